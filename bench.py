@@ -2,7 +2,7 @@
 """bench.py - chunks/s of the squiggle-classification hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config rna004_b512|promethion|progressive]
-                    [--dtype f32|f32_direct|bf16|f16|bf16x3|f16x3]
+                    [--dtype f32|f32_direct|bf16|f16|bf16x3|f16x3] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic reads already resident in HBM:
 MAD-normalise + 12-layer ConvNet forward + softmax, through the C ABI.
@@ -27,6 +27,10 @@ Ranks: with WORLD_SIZE in the environment (torch.distributed.run, one rank per G
 call) and prints rank 0's line; it fails if fewer than N devices are visible.  Reads are independent: every rank steps
 its own shard, there is no data-path collective; the printed value is the whole-job aggregate over the
 max-over-ranks time ("scaling": "weak").
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned, as DIR/probs.npy ([reads, 2] float32;
+promethion_live: rejected.npy / finished.npy, float64 channels of the reads the client was sent).  Inputs and weights are
+seeded, so two builds of the project run with the same arguments compare output for output.
 
 Prints ONE JSON line on rank 0.  Extra objects:
   roofline      conv stack (layers 1..11, the MFMA kernel family): `achieved` = the TFLOP/s the matrix pipe really
@@ -102,6 +106,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-latency", action="store_true", help="skip the per-batch latency loop (profiling runs)")
     ap.add_argument("--no-variants", action="store_true", help="skip the 16-bit / ensemble side measurements")
     ap.add_argument("--no-control-loop", action="store_true", help="skip the ReadUntil replay")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # CPU rehearsal of the rank plumbing (tests)
     ap.add_argument("--stub-fail-rank", type=int, default=None, help=argparse.SUPPRESS)   # tests: this rank dies before the rendezvous
     args = ap.parse_args(argv)
@@ -113,6 +119,8 @@ def parse_args(argv=None):
         args.steps = {"promethion": 3, "promethion_live": 30}.get(args.config, 50)
     if args.warmup is None:
         args.warmup = {"promethion": 1, "promethion_live": 4}.get(args.config, 30)   # ~60 ms: the shader clock needs ~20 steps to settle
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -251,6 +259,10 @@ class Workload:
                               out=self.probs, streams=self.args.streams)
         else:
             self.model.classify_raw(self.sig, self.off, self.ln, self.lens_host, out=self.probs)
+
+    def outputs(self):
+        """what the last step returned to its caller: the class probabilities of every read of the step, [reads, 2]"""
+        return {"probs": self.probs.reshape(-1, 2).cpu().numpy()}
 
 
 def algorithmic_bytes_per_step(channels, lens, esize, fused01=True):
@@ -740,6 +752,9 @@ def run_promethion_live(args, model, lib_dtype, device, rank, world):
             gc.unfreeze()
         ctl.finish()
         rows_timed = csv_rows(out_file + ".csv") - rows_warm
+    if args.dump_outputs:                     # what the client was sent for the last timed batch: the reads' channels
+        write_outputs(args.dump_outputs, {k: np.array([ch for ch, _ in getattr(client, k)[-1]], dtype=np.float64)
+                                          for k in ("rejected", "finished")}, rank)
     lat = np.asarray(list(ctl.batch_latencies)[n_warm:]) * 1e3
     loop = np.asarray(list(ctl.batch_loop_times)[n_warm:]) * 1e3
     phases = np.asarray(list(ctl.batch_phases)[n_warm:]).reshape(-1, len(PHASES)) * 1e3
@@ -872,6 +887,8 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     coarse_ms, conv_calls = model.profile_read()
     model.profile(False)
+    if args.dump_outputs:                     # before the untimed passes below write into the same buffers
+        write_outputs(args.dump_outputs, wl.outputs(), rank)
     per_rank = per_rank_object(elapsed, wl.reads_per_step * args.steps, args.steps, world)
     elapsed = rdist.reduce_scalar(elapsed, "max", device)
     total_chunks = rdist.reduce_scalar(wl.reads_per_step * args.steps, "sum", device)
@@ -1117,6 +1134,29 @@ def write_detail(detail, args):
         return os.path.relpath(path, ROOT)
     except OSError:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def write_outputs(d, arrays, rank=0):
+    """--dump-outputs: each array as d/<name>.npy (rank r > 0: <name>_rank<r>.npy), float64 if it is float64, else float32.
+    Beyond DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded sample of its rows, sorted, and their indices go to
+    <name>_rows.npy: the same rows in every run, so two builds compare output for output."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    suffix = f"_rank{rank}" if rank else ""
+    if sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES:
+        scale = 1.0
+    else:                                                  # sampled rows plus their float64 indices, 1 MB left for headers
+        scale = (DUMP_LIMIT_BYTES - 10 ** 6) / sum(a.nbytes + 8 * (a.shape[0] if a.ndim else 1) for a in arrays.values())
+    for name, a in arrays.items():
+        if scale < 1.0 and a.ndim and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * scale))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(d, f"{name}_rows{suffix}.npy"), rows.astype(np.float64))
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), a)
 
 
 if __name__ == "__main__":

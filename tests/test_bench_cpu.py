@@ -34,6 +34,32 @@ def test_world_size_mismatch_fails_loudly():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_steps_below_one_is_refused():
+    r = _run(["--gpus", "1", "--stub", "--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_keep_dtype_and_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs (bench.write_outputs): float64 stays float64, anything else becomes float32; over the size limit every
+    array keeps the same seeded rows in every run, with their indices beside them; rank r > 0 writes its own names"""
+    import numpy as np
+    import bench
+    probs = np.random.default_rng(1).random((1000, 2)).astype(np.float16)
+    chans = np.arange(10, dtype=np.float64)
+    bench.write_outputs(str(tmp_path / "full"), {"probs": probs, "chans": chans}, rank=3)
+    assert np.load(tmp_path / "full" / "probs_rank3.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "full" / "chans_rank3.npy"), chans)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 ** 6 + 8000)
+    big = np.random.default_rng(2).random((100000, 2))
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"probs": big})
+    rows = np.load(tmp_path / "a" / "probs_rows.npy")
+    got = np.load(tmp_path / "a" / "probs.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "probs_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got, big[rows.astype(np.int64)])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+
+
 def test_more_gpus_than_devices_is_an_error_not_a_one_gpu_run():
     import torch
     if torch.cuda.device_count() >= 16:

@@ -238,6 +238,33 @@ def test_four_ranks_share_the_gpu_on_the_live_config(tmp_path):
     assert out["value"] > 0 and out["reads_received_per_s"] >= out["value"] and out["latency_samples"] == 6
 
 
+def test_bench_dump_outputs_are_what_the_timed_step_returned(dev, tmp_path):
+    """`bench.py --dump-outputs DIR`: the probabilities of the last timed step are those of the same seeded batch classified
+    here; on the live config, the channels of the last timed batch's rejected / finished reads"""
+    from riser_amd.model import Model
+    from riser_amd.preprocess import pack_reads
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    quiet = ["--no-latency", "--no-variants", "--no-control-loop", "--no-cpu-baseline"]
+    runs = {"b64": ["--batch", "64", "--steps", "3", "--warmup", "1", *quiet],
+            "live": ["--config", "promethion_live", "--reads-per-gpu", "64", "--steps", "3", "--warmup", "1"]}
+    for name, args in runs.items():
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args, "--dump-outputs",
+                            str(tmp_path / name)], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+    got = np.load(tmp_path / "b64" / "probs.npy")
+    sigs = synth.make_signals(20260103, 64, 16000)
+    m = Model(synth.make_state_dict(1), synth.Config(), None, "mRNA", dtype="f32w", device=dev)
+    want = m.classify_raw(*pack_reads(list(sigs), dev)).cpu().numpy()
+    m.close()
+    assert got.dtype == np.float32 and got.shape == (64, 2)
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-6)
+    rejected, finished = (np.load(tmp_path / "live" / f"{k}.npy") for k in ("rejected", "finished"))
+    assert rejected.dtype == finished.dtype == np.float64 and rejected.ndim == finished.ndim == 1
+    assert set(rejected.tolist()) <= set(finished.tolist()) <= set(range(1, 65))
+
+
 @pytest.mark.parametrize("dtype", ["f32w", "f32", "bf16x3"])
 def test_length_mismatch_is_contained_on_every_path(dev, dtype):
     """host lengths that disagree with the device's - above AND below - on the fused path of every dtype
