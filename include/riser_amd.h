@@ -354,6 +354,46 @@ RS_API int rs_seqnet_ragged_ok(const rs_seqnet* m);
 RS_API int rs_seqnet_forward_ragged(rs_seqnet* m, const float* d_x /* fp32 [B, ld] */, const int32_t* d_len, int B, int ld, void* d_ws,
                              size_t ws_bytes, float* d_probs, float* d_logits, void* stream);
 
+/*
+ * ABI 2.6: TCN and bottleneck TCN (riser/nets/tcn.py:62-91, riser/nets/tcn_bot.py:63-92; chosen by riser/train.py:175-182
+ * for `model: tcn` / `tcn-bot`; not loadable by the reference's Model).  The host folds weight_norm (g * v / ||v||) and hands
+ * over per temporal block its convs - TCN: two causal k-convs (tcn.py:27-30), TCNBot: 1x1, k, k, 1x1 (tcn_bot.py:27-32) -
+ * each followed by ReLU, the optional 1x1 shortcut (should_apply_shortcut, tcn.py:57-59; null = identity residual), and
+ * base = d_{i+1} / d_i (block 0 has dilation 1).  The block output is relu(convs + residual) (tcn.py:47-51); the head is
+ * linear(x[:, :, -1]) (tcn.py:87) + softmax (riser/model.py:27).
+ * Only the last receptive field of a read matters, and inside it only positions L-1 - d_i * m of block i: the device runs
+ * that cone (csrc/tcn.hip), one fused launch per block, fp32 on the f32-input MFMA.  Cost does not grow with read length.
+ */
+typedef struct rs_tcn_conv {
+    int32_t c_in, c_out, k;
+    int32_t causal;         /* 1: left-padded by (k - 1) * dilation and chomped (k > 1); 0 only for k == 1 */
+    const float* w;         /* HOST fp32 [c_out, c_in, k], weight_norm folded */
+    const float* b;         /* HOST fp32 [c_out] */
+} rs_tcn_conv;
+typedef struct rs_tcn_block {
+    int32_t n_convs;        /* 1..4, chained; at least one with k > 1 */
+    int32_t base;           /* dilation of the next block / this block's (>= 1) */
+    rs_tcn_conv convs[4];
+    int32_t has_shortcut;   /* 1: sc_w / sc_b ([c_out, c_in] / [c_out]); 0: identity (c_in == c_out) */
+    int32_t reserved;
+    const float* sc_w;
+    const float* sc_b;
+} rs_tcn_block;
+typedef struct rs_tcn rs_tcn;
+RS_API int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w /* [2, c_last] */, const float* fc_b,
+                         int c_last, int device, rs_tcn** out);
+RS_API int rs_tcn_destroy(rs_tcn* m);
+/* 1 + sum over the causal convs of (k - 1) * dilation (the reference's get_receptive_field), saturated at INT64_MAX */
+RS_API int64_t rs_tcn_receptive_field(const rs_tcn* m);
+RS_API size_t rs_tcn_workspace_bytes(const rs_tcn* m, int B, int ld);
+/* largest B whose activation buffers stay inside the 2 GiB buffer window for reads of pitch ld; callers split bigger batches */
+RS_API int rs_tcn_max_batch(const rs_tcn* m, int ld);
+/* Read b is d_x[b * ld .. b * ld + d_len[b]) (d_len in [1, ld]; a larger value is read as ld), right-aligned: its last sample
+ * is the position the head classifies, and every position before its start is zero padding.  A uniform batch is the same call
+ * with equal lengths.  A read's result does not depend on ld or on the other reads, bit for bit.  d_logits may be null. */
+RS_API int rs_tcn_forward_ragged(rs_tcn* m, const float* d_x /* fp32 [B, ld] */, const int32_t* d_len, int B, int ld, void* d_ws,
+                                 size_t ws_bytes, float* d_probs /* [B, 2] */, float* d_logits, void* stream);
+
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag

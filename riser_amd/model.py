@@ -75,7 +75,18 @@ class Model:
         self.device = self._get_device(device)
         if logger is not None:
             logger.info('Using %s device', self.device)
-        if getattr(config, "model", None) == "resnet" or (not hasattr(config, "cnn") and hasattr(config, "resnet")):
+        kind = getattr(config, "model", None)
+        is_resnet = kind == "resnet" or (not hasattr(config, "cnn") and hasattr(config, "resnet"))
+        if not is_resnet and (kind == "tcn-bot" or (kind != "tcn" and not hasattr(config, "cnn") and hasattr(config, "tcnbot"))):
+            # `config.tcnbot` (riser/nets/tcn_bot.py:63-85) or `config.tcn` (riser/nets/tcn.py:62-82), what riser/train.py:175-182
+            # trains for `model: tcn-bot` / `tcn`: the receptive cone of the last position (csrc/tcn.hip), behind the same
+            # surface as the ResNet below
+            self._init_tcn(state, config.tcnbot, True, dtype)
+            return
+        if not is_resnet and (kind == "tcn" or (not hasattr(config, "cnn") and hasattr(config, "tcn"))):
+            self._init_tcn(state, config.tcn, False, dtype)
+            return
+        if is_resnet:
             # `config.resnet` (riser/nets/resnet.py:72-99: channels, kernel, padding, stride, block, n_layers, blocks,
             # n_classes) instead of `config.cnn`: the reference's second architecture.  Its own Model hard-wires ConvNet
             # (riser/model.py:13) and ships no ResNet config or weights; here the same Model surface - classify, the batched
@@ -285,6 +296,21 @@ class Model:
             else:
                 lo = mid + 1
         self.min_length = lo
+
+    def _init_tcn(self, state, tc, bottleneck: bool, dtype: str):
+        from .tcn import TCNNet, build_tcn_program
+        if dtype not in ("f32w", "f32"):
+            raise ValueError(f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA)")
+        sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
+        blocks, fw, fb = build_tcn_program(sd, tc, bottleneck)
+        self.classifier, self._fc_positions = "gap_fc", 0
+        self.channels = [int(tc.n_filters)] * int(tc.n_layers)
+        self.n_layers = len(self.channels)
+        self._keep, self._h, self.model = [], None, self
+        self._seq = TCNNet(blocks, fw, fb, device=self.device, dtype=dtype)
+        self.dtype = self._seq.dtype
+        self._ws = Workspace(self.device)
+        self.min_length = 1                 # causal convs: any read of one sample or more has a last position
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -336,3 +336,42 @@ def make_resnet_state_dict(seed: int, cfg: dict = None) -> dict:
     sd["decoder.2.weight"] = (u(cfg["n_classes"] * in_ch) * np.float32(0.3)).reshape(cfg["n_classes"], in_ch).astype(np.float32)
     sd["decoder.2.bias"] = (u(cfg["n_classes"]) * np.float32(0.1)).astype(np.float32)
     return sd
+
+
+TCN_BENCH_CFG = dict(in_channels=1, n_filters=64, kernel=3, dilation=2, n_layers=8, dropout=0.2, n_classes=2)
+
+
+def make_tcn_state_dict(seed: int, cfg: dict = None, bottleneck: bool = False) -> dict:
+    """Reference-format TCN / TCNBot state dict (riser/nets/tcn.py:62-82, tcn_bot.py:63-85; weight_norm's weight_g /
+    weight_v, every block's shortcut present) from the integer hash.  weight_g scales each output channel to a gain near 1,
+    so activations stay O(1) through any depth."""
+    cfg = cfg or TCN_BENCH_CFG
+    sd, stream = {}, [0]
+
+    def u(n):
+        stream[0] += 1
+        return uniform_pm1(seed, 7000 + stream[0], n)
+
+    def wn_conv(name, co, ci, k):
+        sd[name + ".weight_v"] = u(co * ci * k).reshape(co, ci, k).astype(np.float32)
+        sd[name + ".weight_g"] = (1.0 + 0.3 * u(co)).reshape(co, 1, 1).astype(np.float32)
+        sd[name + ".bias"] = (u(co) * np.float32(0.05)).astype(np.float32)
+
+    nf, k = cfg["n_filters"], cfg["kernel"]
+    for i in range(cfg["n_layers"]):
+        ci = cfg["in_channels"] if i == 0 else nf
+        pre = f"layers.{i}"
+        if bottleneck:
+            mid = nf // 4
+            wn_conv(pre + ".blocks.0.0", mid, ci, 1)
+            wn_conv(pre + ".blocks.1.0", mid, mid, k)
+            wn_conv(pre + ".blocks.2.0", mid, mid, k)
+            wn_conv(pre + ".blocks.3.0", nf, mid, 1)
+        else:
+            wn_conv(pre + ".blocks.0.0", nf, ci, k)
+            wn_conv(pre + ".blocks.1.0", nf, nf, k)
+        sd[pre + ".shortcut.weight"] = (u(nf * ci) * np.float32(np.sqrt(3.0 / ci))).reshape(nf, ci, 1).astype(np.float32)
+        sd[pre + ".shortcut.bias"] = (u(nf) * np.float32(0.05)).astype(np.float32)
+    sd["linear.weight"] = (u(cfg["n_classes"] * nf) * np.float32(0.3)).reshape(cfg["n_classes"], nf).astype(np.float32)
+    sd["linear.bias"] = (u(cfg["n_classes"]) * np.float32(0.1)).astype(np.float32)
+    return sd

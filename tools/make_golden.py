@@ -13,6 +13,8 @@ Reference entry points exercised:
   F2  Model.classify / ConvNet.forward        riser/model.py:22-28, riser/nets/cnn.py:43-65  (F2b: depth > 1 / odd kernels; F2c: `gap` head; F2d: `fc` head)
   F3  SequencerControl.target                 riser/control.py:11-124 (fake client)
   F4  SignalProcessor.get_polyA_end           riser/preprocess.py:42-79
+  F5  ResNet.forward                          riser/nets/resnet.py
+  F6  TCN.forward / TCNBot.forward            riser/nets/tcn.py, riser/nets/tcn_bot.py
 """
 import json
 import logging
@@ -436,10 +438,66 @@ def f5_resnet():
     np.savez_compressed(os.path.join(OUT, "resnet.npz"), **out)
 
 
+TCN_CFGS = {
+    # name: (bottleneck, config); n_filters 18 and 36 leave channel counts off the multiples of 4 (padding paths)
+    "tcn_k3_b2": (False, dict(in_channels=1, n_filters=24, kernel=3, dilation=2, n_layers=5, dropout=0.2, n_classes=2)),
+    "tcn_k5_b3": (False, dict(in_channels=1, n_filters=18, kernel=5, dilation=3, n_layers=4, dropout=0.2, n_classes=2)),
+    "bot_k3": (True, dict(in_channels=1, n_filters=32, kernel=3, dilation=2, n_layers=5, dropout=0.2, n_classes=2)),
+    "bot_k5": (True, dict(in_channels=1, n_filters=36, kernel=5, dilation=2, n_layers=4, dropout=0.2, n_classes=2)),
+}
+
+
+def tcn_lengths(rf):
+    """below the receptive field, at it, one past it, and well above it"""
+    return (max(2, rf // 3), rf, rf + 1, 4097, 12000)
+
+
+def f6_tcn():
+    """reference TCN / TCNBot (riser/nets/tcn.py, tcn_bot.py) in eval mode with randomised weights: weight_v, a weight_g
+    that is not ||v|| (weight_norm's initial value would hide folding bugs), non-zero biases, every shortcut (used or not)."""
+    from nets.tcn import TCN
+    from nets.tcn_bot import TCNBot
+    out = {}
+    rng = np.random.default_rng(4242)
+    torch.manual_seed(4242)
+    for name, (bot, cfg) in TCN_CFGS.items():
+        net = (TCNBot if bot else TCN)(types.SimpleNamespace(**cfg))
+        sd = net.state_dict()
+        new = {}
+        for k, v in sd.items():
+            if k.endswith("weight_g"):
+                new[k] = torch.from_numpy(rng.uniform(0.5, 1.5, v.shape).astype(np.float32))
+            elif v.dim() == 1:                                              # biases
+                new[k] = torch.from_numpy((rng.standard_normal(v.shape) * 0.1).astype(np.float32))
+            else:                                                           # weight_v, shortcut and linear weights
+                fan_in = int(np.prod(v.shape[1:]))
+                new[k] = torch.from_numpy((rng.standard_normal(v.shape) * np.sqrt(1.0 / fan_in)).astype(np.float32))
+        net.load_state_dict(new)
+        net.eval()
+        rf = net.get_receptive_field(cfg["kernel"], cfg["n_layers"]) if bot else \
+            net.get_receptive_field(cfg["kernel"], cfg["n_layers"], cfg["dilation"])
+        lens = tcn_lengths(rf)
+        proc = SignalProcessor(Kit.create_from_version("RNA004"))
+        for L in lens:
+            sigs = synth.make_signals(SIG_SEED, 3, L, first_read=60)
+            x = np.stack([proc.mad_normalise(s.copy()) for s in sigs]).astype(np.float32)
+            with torch.no_grad():
+                logits = net(torch.from_numpy(x))
+                probs = torch.softmax(logits, dim=1)
+            out[f"{name}.L{L}.logits"] = logits.numpy()
+            out[f"{name}.L{L}.probs"] = probs.numpy()
+        for k, v in new.items():
+            out[f"{name}.sd.{k}"] = v.numpy()
+        out[f"{name}.cfg"] = np.array(json.dumps(dict(cfg, model="tcn-bot" if bot else "tcn", rf=int(rf),
+                                                      lengths=[int(v) for v in lens])))
+        print("F6:", name, "RF", rf, out[f"{name}.L4097.probs"][:, 1])
+    np.savez_compressed(os.path.join(OUT, "tcn.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5"]
+    which = sys.argv[1:] or ["f1", "f2", "f3", "f4", "f5", "f6"]
     if "f1" in which:
         f1_normalise()
     if "f1b" in which or "f1" in which:
@@ -458,3 +516,5 @@ if __name__ == "__main__":
         f3_control()
     if "f5" in which:
         f5_resnet()
+    if "f6" in which:
+        f6_tcn()
