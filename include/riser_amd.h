@@ -393,6 +393,14 @@ RS_API int rs_tcn_max_batch(const rs_tcn* m, int ld);
  * with equal lengths.  A read's result does not depend on ld or on the other reads, bit for bit.  d_logits may be null. */
 RS_API int rs_tcn_forward_ragged(rs_tcn* m, const float* d_x /* fp32 [B, ld] */, const int32_t* d_len, int B, int ld, void* d_ws,
                                  size_t ws_bytes, float* d_probs /* [B, 2] */, float* d_logits, void* stream);
+/* ABI 2.7: arithmetic of a TCN's temporal blocks.  RS_BF16X3 runs every conv of every block (the 1x1 shortcut included) in
+ * split precision on the bf16 MFMA (csrc/tcn_x3.hip): each activation and weight is hi = bf16(v), lo = bf16(v - hi), a product
+ * is hi*hi + lo*hi + hi*lo with fp32 accumulation; bias, ReLU, the residual add and the head stay fp32.  RS_F32 / RS_F32W go
+ * back to fp32 (the default), whose bits are those of a freshly created handle.  Any other dtype, or a null handle, returns
+ * RS_ERR_ARG.  The split weights are packed at rs_tcn_create and freed by rs_tcn_destroy.  Both modes keep the same fp32
+ * activation buffers, so rs_tcn_workspace_bytes and rs_tcn_max_batch report the same figures in either.  A read in a ragged
+ * batch gets the bits it gets alone in either mode.  Not safe to call while a forward of the handle is being enqueued. */
+RS_API int rs_tcn_set_mode(rs_tcn* m, int dtype);
 
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path

@@ -17,7 +17,10 @@
 // The GEMM M dimension is reads x positions: late blocks have a handful of positions per read and tile across reads.
 // tcn_head_kernel runs Linear(n_filters -> 2) + softmax on the one remaining position.  Every output element is a fixed
 // k-ordered fmaf chain whatever the tile, the batch or the row pitch: a read's result is that of the read alone, bit for bit.
+// rs_tcn_set_mode(m, RS_BF16X3) runs the blocks on csrc/tcn_x3.hip instead (split precision on the bf16 MFMA); the head and
+// the activation buffers are shared.
 #include "common.hpp"
+#include "tcn_x3.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -200,6 +203,8 @@ struct ConvDev {
     int c_in = 0, c_out = 0, cpi = 0, cpo = 0, np = 0, k = 0;
     float* w = nullptr;         // [k][cpi][np]: element (tap t reads m + t, ci, co) = w_ref[co][ci][k - 1 - t]
     float* b = nullptr;         // [np]
+    unsigned short* xw = nullptr;   // RS_BF16X3: tcn_x3_pack planes
+    int xsteps = 0;
 };
 
 struct BlockDev {
@@ -208,12 +213,15 @@ struct BlockDev {
     ConvDev conv[kMaxConvs];
     float* sw = nullptr;        // [cp_in][np_out]
     float* sb = nullptr;
+    unsigned short* xsw = nullptr;  // RS_BF16X3: the shortcut's tcn_x3_pack planes
+    int xsw_steps = 0;
     int span = 0;               // sum of (k - 1) over the block's causal convs
 };
 
-hipError_t upload(float** dst, const std::vector<float>& v) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * 4);
-    if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * 4, hipMemcpyHostToDevice);
+template <class T>
+hipError_t upload(T** dst, const std::vector<T>& v) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
     return e;
 }
 
@@ -227,6 +235,7 @@ struct rs_tcn {
     float* d_fcb = nullptr;
     int c_last = 0;
     int64_t rf = 1;
+    int mode = 0;               // rs_tcn_set_mode: 0 fp32 (f32-input MFMA), 1 split precision on the bf16 MFMA
 };
 
 namespace rs {
@@ -288,6 +297,89 @@ size_t buffer_bytes(const rs_tcn* m, int64_t B, int ld) {
 }
 
 constexpr int64_t kWindow = (int64_t(1) << 31) - 4096;     // every activation buffer stays inside 2 GiB
+
+// block i of an RS_BF16X3 forward (csrc/tcn_x3.hip): the tile choice of the fp32 path on the split LDS layout
+int launch_block_x3(const BlockDev& bd, int i, const float* in, const int32_t* d_len, float* out, int B, int ld, int in_rows,
+                    int out_rows, hipStream_t st) {
+    int k[kMaxConvs], cpi[kMaxConvs], cpo[kMaxConvs];
+    for (int j = 0; j < bd.nconv; ++j) {
+        k[j] = bd.conv[j].k;
+        cpi[j] = tcn_cp8(bd.conv[j].c_in);
+        cpo[j] = tcn_cp8(bd.conv[j].c_out);
+    }
+    auto plan = [&](int T, int nb) { return tcn_x3_plan(bd.nconv, k, cpi, cpo, bd.jk, bd.base, T, nb); };
+    int T = std::min(out_rows, 64);
+    while (T > 1 && plan(T, 1).lds_bytes > (size_t)kLdsBudget) --T;
+    int nb = 1;
+    if (T == out_rows) {
+        nb = std::max(1, std::min(B, 64 / T));
+        while (nb > 1 && plan(T, nb).lds_bytes > (size_t)kLdsBudget) --nb;
+    }
+    const TcnX3Plan p = plan(T, nb);
+    if (p.lds_bytes > (size_t)kLdsBudget) {
+        set_error("rs_tcn_forward_ragged: block %d is too wide for one tile of LDS", i);
+        return RS_ERR_ARG;
+    }
+    TcnX3Args a;
+    memset(&a, 0, sizeof(a));
+    a.x = in;
+    a.len = d_len;
+    a.y = out;
+    a.B = B;
+    a.ld = ld;
+    a.first = i == 0;
+    a.dil = std::min<int64_t>(bd.dil, (int64_t)ld + 1);
+    a.r = bd.base;
+    a.in_rows = in_rows;
+    a.out_rows = out_rows;
+    a.cp_in = cp4(bd.c_in);
+    a.cp_out = cp4(bd.c_out);
+    a.T = T;
+    a.nb = nb;
+    a.tiles_pos = (out_rows + T - 1) / T;
+    a.rows_in = p.rows_in;
+    a.nconv = bd.nconv;
+    for (int j = 0; j < bd.nconv; ++j) {
+        const ConvDev& c = bd.conv[j];
+        a.w[j] = c.xw;
+        a.b[j] = c.b;
+        a.k[j] = c.k;
+        a.cpi[j] = cpi[j];
+        a.cpo[j] = cpo[j];
+        a.np[j] = c.np;
+        a.steps[j] = c.xsteps;
+        a.rows[j] = p.rows[j];
+        a.step[j] = j == bd.jk ? bd.base : 1;
+        a.ostride[j] = j >= bd.jk ? bd.base : 1;
+        a.src[j] = j == 0 ? 0 : 1 + ((j - 1) & 1);
+        a.dst[j] = j + 1 == bd.nconv ? -1 : 1 + (j & 1);
+    }
+    a.sw = bd.xsw;
+    a.sb = bd.sb;
+    a.sw_steps = bd.xsw_steps;
+    for (int d = 0; d < 3; ++d) {
+        a.off[d] = p.off[d];
+        a.pitch[d] = p.pitch[d];
+        a.plane[d] = p.plane[d];
+    }
+    for (int j = 0; j < bd.nconv; ++j) {
+        const int s = a.src[j], d = std::max(a.dst[j], 0);
+        a.s_off[j] = p.off[s];
+        a.s_pitch[j] = p.pitch[s];
+        a.s_plane[j] = p.plane[s];
+        a.s_rows[j] = s == 0 ? p.rows_in : p.rows[j - 1];
+        a.d_off[j] = p.off[d];
+        a.d_pitch[j] = p.pitch[d];
+        a.d_plane[j] = p.plane[d];
+    }
+    const int64_t grid = (int64_t)((B + nb - 1) / nb) * a.tiles_pos;
+    if (grid > INT32_MAX) {
+        set_error("rs_tcn_forward_ragged: grid too large: split the batch");
+        return RS_ERR_ARG;
+    }
+    RS_HIP(tcn_x3_launch(a, (unsigned)grid, p.lds_bytes, st));
+    return RS_OK;
+}
 
 }  // namespace
 }  // namespace rs
@@ -351,6 +443,8 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
             }
             e = upload(&cd.w, w);
             if (e == hipSuccess) e = upload(&cd.b, b);
+            int xnp = 0;
+            if (e == hipSuccess) e = upload(&cd.xw, tcn_x3_pack(c.w, c.c_out, c.c_in, c.k, &cd.xsteps, &xnp));
             if (c.k > 1) {
                 bd.span += c.k - 1;
                 const int64_t add = (int64_t)(c.k - 1) * dil;
@@ -366,6 +460,8 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
             }
             e = upload(&bd.sw, w);
             if (e == hipSuccess) e = upload(&bd.sb, b);
+            int xnp = 0;
+            if (e == hipSuccess) e = upload(&bd.xsw, tcn_x3_pack(s.sc_w, bd.c_out, bd.c_in, 1, &bd.xsw_steps, &xnp));
         }
         m->blocks.push_back(bd);
         dil = std::min<int64_t>(kMaxDil, dil * s.base);
@@ -393,13 +489,33 @@ int rs_tcn_destroy(rs_tcn* m) {
         for (int j = 0; j < kMaxConvs; ++j) {
             if (b.conv[j].w) (void)hipFree(b.conv[j].w);
             if (b.conv[j].b) (void)hipFree(b.conv[j].b);
+            if (b.conv[j].xw) (void)hipFree(b.conv[j].xw);
         }
         if (b.sw) (void)hipFree(b.sw);
         if (b.sb) (void)hipFree(b.sb);
+        if (b.xsw) (void)hipFree(b.xsw);
     }
     if (m->d_fcw) (void)hipFree(m->d_fcw);
     if (m->d_fcb) (void)hipFree(m->d_fcb);
     delete m;
+    return RS_OK;
+}
+
+int rs_tcn_set_mode(rs_tcn* m, int dtype) {
+    if (!m) {
+        set_error("rs_tcn_set_mode: null program");
+        return RS_ERR_ARG;
+    }
+    if (dtype == RS_F32 || dtype == RS_F32W) {
+        m->mode = 0;
+        return RS_OK;
+    }
+    if (dtype != RS_BF16X3) {
+        set_error("rs_tcn_set_mode: a TCN runs in RS_F32 / RS_F32W (f32-input MFMA) or RS_BF16X3 (split precision on the "
+                  "bf16 MFMA)");
+        return RS_ERR_ARG;
+    }
+    m->mode = 1;
     return RS_OK;
 }
 
@@ -443,6 +559,12 @@ int rs_tcn_forward_ragged(rs_tcn* m, const float* d_x, const int32_t* d_len, int
     for (int i = 0; i < n; ++i) {
         const BlockDev& bd = m->blocks[i];
         const int out_rows = (int)need[i + 1];
+        if (m->mode == 1) {
+            const int rc = launch_block_x3(bd, i, in, d_len, buf[i & 1], B, ld, (int)need[i], out_rows, st);
+            if (rc != RS_OK) return rc;
+            in = buf[i & 1];
+            continue;
+        }
         // tile: up to 64 output positions of one read, or - where a read has fewer - several reads, inside the LDS budget
         int T = std::min(out_rows, 64);
         while (T > 1 && plan_tile(bd, T, 1).lds_bytes > (size_t)kLdsBudget) --T;

@@ -299,8 +299,9 @@ class Model:
 
     def _init_tcn(self, state, tc, bottleneck: bool, dtype: str):
         from .tcn import TCNNet, build_tcn_program
-        if dtype not in ("f32w", "f32"):
-            raise ValueError(f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA)")
+        if dtype not in ("f32w", "f32", "bf16x3"):
+            raise ValueError(f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'bf16x3' (split "
+                             "precision on the bf16 MFMA)")
         sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
         blocks, fw, fb = build_tcn_program(sd, tc, bottleneck)
         self.classifier, self._fc_positions = "gap_fc", 0

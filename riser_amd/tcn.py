@@ -5,7 +5,8 @@ the logits depend on the last receptive field of the read and, inside it, on a s
 (dilation d_i) is needed only at positions L-1 - d_i * m, m = 0, 1, ...  On that subsequence a k-tap conv of dilation d_i
 is a dense k-tap causal conv, and between block i and block i+1 the sequence is subsampled by base = d_{i+1} / d_i,
 counting back from the last sample.  This module folds a reference state dict into per-block conv lists (pure numpy,
-no GPU), works out the per-block windows of that cone, and drives the device program of csrc/tcn.hip (rs_tcn_*).
+no GPU), works out the per-block windows of that cone, and drives the device program of csrc/tcn.hip (rs_tcn_*; in dtype
+'bf16x3' the blocks run csrc/tcn_x3.hip).
 """
 from __future__ import annotations
 
@@ -139,9 +140,12 @@ class TCNNet:
     ragged_ok = True
 
     def __init__(self, blocks, fw, fb, device, dtype: str = "f32"):
-        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32"}.get(dtype)
+        """dtype: 'f32' / 'f32w' / 'fp32' (fp32 on the f32-input MFMA) or 'bf16x3' (every conv in split precision on the
+        bf16 MFMA, csrc/tcn_x3.hip: rs_tcn_set_mode)"""
+        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32", "bf16x3": "bf16x3"}.get(dtype)
         if self.dtype is None:
-            raise ValueError(f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (f32-input MFMA)")
+            raise ValueError(f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (f32-input MFMA) or 'bf16x3' (split precision "
+                             "on the bf16 MFMA)")
         nv.require_gpu()
         d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
@@ -162,6 +166,8 @@ class TCNNet:
                                         self.device.index, C.byref(h)), "rs_tcn_create")
         self._h = h
         self._ws = None
+        if self.dtype == "bf16x3":
+            nv.check(nv.lib().rs_tcn_set_mode(h, nv.RS_BF16X3), "rs_tcn_set_mode")
 
     @property
     def receptive_field(self) -> int:
