@@ -383,7 +383,8 @@ typedef struct rs_tcn rs_tcn;
 RS_API int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w /* [2, c_last] */, const float* fc_b,
                          int c_last, int device, rs_tcn** out);
 RS_API int rs_tcn_destroy(rs_tcn* m);
-/* 1 + sum over the causal convs of (k - 1) * dilation (the reference's get_receptive_field), saturated at INT64_MAX */
+/* 1 + sum over the causal convs of (k - 1) * dilation (the reference's get_receptive_field), saturated at INT64_MAX; exact for
+ * dilations past any read length too (before ABI 2.8 a dilation above 2^40 was counted as 2^40) */
 RS_API int64_t rs_tcn_receptive_field(const rs_tcn* m);
 RS_API size_t rs_tcn_workspace_bytes(const rs_tcn* m, int B, int ld);
 /* largest B whose activation buffers stay inside the 2 GiB buffer window for reads of pitch ld; callers split bigger batches */
@@ -401,6 +402,10 @@ RS_API int rs_tcn_forward_ragged(rs_tcn* m, const float* d_x /* fp32 [B, ld] */,
  * activation buffers, so rs_tcn_workspace_bytes and rs_tcn_max_batch report the same figures in either.  A read in a ragged
  * batch gets the bits it gets alone in either mode.  Not safe to call while a forward of the handle is being enqueued. */
 RS_API int rs_tcn_set_mode(rs_tcn* m, int dtype);
+/* ABI 2.8: the tile the forward launches for block `block` (0-based) of a batch of B reads of pitch ld in the handle's current
+ * mode: *T output positions of *nb reads per workgroup, *tiles_pos tiles along the positions of a read.  Read-only: it changes
+ * no launch.  A bad argument, or a block too wide for one tile of LDS (what the forward refuses), returns RS_ERR_ARG. */
+RS_API int rs_tcn_tile_plan(const rs_tcn* m, int block, int B, int ld, int* T, int* nb, int* tiles_pos);
 
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path

@@ -26,6 +26,7 @@ SYMBOLS = (
     "rs_debug_capture_layer", "rs_polya_end_resume", "rs_model_saturated",
     "rs_seqnet_create", "rs_seqnet_destroy", "rs_seqnet_workspace_bytes", "rs_seqnet_forward", "rs_seqnet_set_mode", "rs_seqnet_ragged_ok", "rs_seqnet_forward_ragged", "rs_seqnet_max_batch",
     "rs_tcn_create", "rs_tcn_destroy", "rs_tcn_receptive_field", "rs_tcn_workspace_bytes", "rs_tcn_max_batch", "rs_tcn_forward_ragged", "rs_tcn_set_mode",
+    "rs_tcn_tile_plan",
 )
 
 
@@ -131,6 +132,8 @@ def lib():
     L.rs_tcn_forward_ragged.argtypes = [vp, vp, vp, i32, i32, vp, sz, vp, vp, vp]
     L.rs_tcn_set_mode.restype = i32
     L.rs_tcn_set_mode.argtypes = [vp, i32]
+    L.rs_tcn_tile_plan.restype = i32
+    L.rs_tcn_tile_plan.argtypes = [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32

@@ -287,6 +287,31 @@ TilePlan plan_tile(const BlockDev& b, int T, int nb) {
     return p;
 }
 
+// the tile of a block in `mode` (rs_tcn::mode) for out_rows outputs per read: up to 64 output positions of one read, or -
+// where a read has fewer - several reads, inside the LDS budget.  The forward and rs_tcn_tile_plan both take it from here.
+// Returns the tile's LDS bytes: above kLdsBudget, the block is too wide for one tile even at T = 1.
+size_t choose_tile(const BlockDev& bd, int mode, int B, int out_rows, int* T_out, int* nb_out) {
+    int k[kMaxConvs], cpi[kMaxConvs], cpo[kMaxConvs];
+    for (int j = 0; j < bd.nconv; ++j) {
+        k[j] = bd.conv[j].k;
+        cpi[j] = tcn_cp8(bd.conv[j].c_in);
+        cpo[j] = tcn_cp8(bd.conv[j].c_out);
+    }
+    auto lds = [&](int T, int nb) {
+        return mode == 1 ? tcn_x3_plan(bd.nconv, k, cpi, cpo, bd.jk, bd.base, T, nb).lds_bytes : plan_tile(bd, T, nb).lds_bytes;
+    };
+    int T = std::min(out_rows, 64);
+    while (T > 1 && lds(T, 1) > (size_t)kLdsBudget) --T;
+    int nb = 1;
+    if (T == out_rows) {
+        nb = std::max(1, std::min(B, 64 / T));
+        while (nb > 1 && lds(T, nb) > (size_t)kLdsBudget) --nb;
+    }
+    *T_out = T;
+    *nb_out = nb;
+    return lds(T, nb);
+}
+
 size_t buffer_bytes(const rs_tcn* m, int64_t B, int ld) {
     std::vector<int64_t> need;
     tcn_windows(m, ld, need);
@@ -295,6 +320,9 @@ size_t buffer_bytes(const rs_tcn* m, int64_t B, int ld) {
         mx = std::max(mx, (size_t)need[i + 1] * (size_t)rs::cp4(m->blocks[i].c_out) * 4);
     return ((size_t)B * mx + 255) / 256 * 256;
 }
+
+// a * b for a, b >= 0, saturated at INT64_MAX
+int64_t sat_mul(int64_t a, int64_t b) { return (a != 0 && b > INT64_MAX / a) ? INT64_MAX : a * b; }
 
 constexpr int64_t kWindow = (int64_t(1) << 31) - 4096;     // every activation buffer stays inside 2 GiB
 
@@ -307,15 +335,9 @@ int launch_block_x3(const BlockDev& bd, int i, const float* in, const int32_t* d
         cpi[j] = tcn_cp8(bd.conv[j].c_in);
         cpo[j] = tcn_cp8(bd.conv[j].c_out);
     }
-    auto plan = [&](int T, int nb) { return tcn_x3_plan(bd.nconv, k, cpi, cpo, bd.jk, bd.base, T, nb); };
-    int T = std::min(out_rows, 64);
-    while (T > 1 && plan(T, 1).lds_bytes > (size_t)kLdsBudget) --T;
-    int nb = 1;
-    if (T == out_rows) {
-        nb = std::max(1, std::min(B, 64 / T));
-        while (nb > 1 && plan(T, nb).lds_bytes > (size_t)kLdsBudget) --nb;
-    }
-    const TcnX3Plan p = plan(T, nb);
+    int T = 1, nb = 1;
+    choose_tile(bd, 1, B, out_rows, &T, &nb);
+    const TcnX3Plan p = tcn_x3_plan(bd.nconv, k, cpi, cpo, bd.jk, bd.base, T, nb);
     if (p.lds_bytes > (size_t)kLdsBudget) {
         set_error("rs_tcn_forward_ragged: block %d is too wide for one tile of LDS", i);
         return RS_ERR_ARG;
@@ -402,6 +424,7 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
     m->device = device;
     m->c_last = c_last;
     int64_t dil = 1, rf = 1;
+    int64_t rf_dil = 1;                 // the receptive field's dilation: not clamped to kMaxDil, saturated at INT64_MAX
     hipError_t e = hipSuccess;
     for (int i = 0; i < n_blocks && e == hipSuccess; ++i) {
         const rs_tcn_block& s = blocks[i];
@@ -447,7 +470,7 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
             if (e == hipSuccess) e = upload(&cd.xw, tcn_x3_pack(c.w, c.c_out, c.c_in, c.k, &cd.xsteps, &xnp));
             if (c.k > 1) {
                 bd.span += c.k - 1;
-                const int64_t add = (int64_t)(c.k - 1) * dil;
+                const int64_t add = sat_mul(c.k - 1, rf_dil);
                 rf = (rf > INT64_MAX - add) ? INT64_MAX : rf + add;
             }
         }
@@ -465,6 +488,7 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
         }
         m->blocks.push_back(bd);
         dil = std::min<int64_t>(kMaxDil, dil * s.base);
+        rf_dil = sat_mul(rf_dil, s.base);
     }
     if (e == hipSuccess && m->blocks.back().c_out != c_last) {
         rs_tcn_destroy(m);
@@ -521,6 +545,25 @@ int rs_tcn_set_mode(rs_tcn* m, int dtype) {
 
 int64_t rs_tcn_receptive_field(const rs_tcn* m) { return m ? m->rf : 0; }
 
+int rs_tcn_tile_plan(const rs_tcn* m, int block, int B, int ld, int* T, int* nb, int* tiles_pos) {
+    if (!m || block < 0 || block >= (int)m->blocks.size() || B < 1 || ld < 1 || !T || !nb || !tiles_pos) {
+        set_error("rs_tcn_tile_plan: bad argument");
+        return RS_ERR_ARG;
+    }
+    std::vector<int64_t> need;
+    tcn_windows(m, ld, need);
+    const int out_rows = (int)need[block + 1];
+    int t = 1, n = 1;
+    if (choose_tile(m->blocks[block], m->mode, B, out_rows, &t, &n) > (size_t)kLdsBudget) {
+        set_error("rs_tcn_tile_plan: block %d is too wide for one tile of LDS", block);
+        return RS_ERR_ARG;
+    }
+    *T = t;
+    *nb = n;
+    *tiles_pos = (out_rows + t - 1) / t;
+    return RS_OK;
+}
+
 size_t rs_tcn_workspace_bytes(const rs_tcn* m, int B, int ld) {
     if (!m || B < 1 || ld < 1) return 0;
     return 2 * buffer_bytes(m, B, ld);
@@ -565,14 +608,8 @@ int rs_tcn_forward_ragged(rs_tcn* m, const float* d_x, const int32_t* d_len, int
             in = buf[i & 1];
             continue;
         }
-        // tile: up to 64 output positions of one read, or - where a read has fewer - several reads, inside the LDS budget
-        int T = std::min(out_rows, 64);
-        while (T > 1 && plan_tile(bd, T, 1).lds_bytes > (size_t)kLdsBudget) --T;
-        int nb = 1;
-        if (T == out_rows) {
-            nb = std::max(1, std::min(B, 64 / T));
-            while (nb > 1 && plan_tile(bd, T, nb).lds_bytes > (size_t)kLdsBudget) --nb;
-        }
+        int T = 1, nb = 1;
+        choose_tile(bd, 0, B, out_rows, &T, &nb);
         const TilePlan p = plan_tile(bd, T, nb);
         if (p.lds_bytes > (size_t)kLdsBudget) {
             set_error("rs_tcn_forward_ragged: block %d is too wide for one tile of LDS", i);

@@ -10,6 +10,7 @@ import pytest
 from oracle import riser_oracle as ro
 from riser_amd import synth
 from riser_amd import tcn as T
+from tests.tcn_ref import cone_forward, dense_forward
 
 NAMES = ["tcn_k3_b2", "tcn_k5_b3", "bot_k3", "bot_k5"]
 
@@ -37,75 +38,6 @@ def _inputs(L):
 def _config(cfg):
     key = "tcnbot" if cfg["model"] == "tcn-bot" else "tcn"
     return types.SimpleNamespace(model=cfg["model"], **{key: _ns(cfg)})
-
-
-def dense_forward(blocks, fw, fb, x):
-    """the reference's forward on the folded weights: every conv causal (left pad (k-1) d, no right side), ReLU after
-    each, relu(convs + residual), Linear on the last position.  float64."""
-    import torch
-    import torch.nn.functional as F
-    h = torch.from_numpy(np.asarray(x, dtype=np.float64))[:, None, :]
-    for b in blocks:
-        d = b["dilation"]
-        y = h
-        for cv in b["convs"]:
-            w = torch.from_numpy(cv["w"].astype(np.float64))
-            pad = (cv["k"] - 1) * d if cv["causal"] else 0
-            y = F.relu(F.conv1d(F.pad(y, (pad, 0)), w, torch.from_numpy(cv["b"].astype(np.float64)),
-                                dilation=d if cv["causal"] else 1))
-        if b["shortcut"] is not None:
-            res = F.conv1d(h, torch.from_numpy(b["shortcut"][0].astype(np.float64))[:, :, None],
-                           torch.from_numpy(b["shortcut"][1].astype(np.float64)))
-        else:
-            res = h
-        h = F.relu(y + res)
-    return (h[:, :, -1] @ torch.from_numpy(fw.astype(np.float64)).T + torch.from_numpy(fb.astype(np.float64))).numpy()
-
-
-def cone_forward(blocks, fw, fb, x, ld=None):
-    """the formulation of csrc/tcn.hip: block i holds positions L-1 - d_i m (m < windows()[i]) position-major, counting
-    back from the last sample; every value at a position below 0 is exactly 0; inside a block the convs up to the last
-    k-conv run dense over m, that conv and what follows it only at m = base * m'.  x: [B, L] (one length)."""
-    x = np.asarray(x, dtype=np.float64)
-    B, L = x.shape
-    need = T.windows(blocks, ld or L)
-    m0 = np.arange(need[0])
-    cur = np.where(L - 1 - m0 >= 0, x[:, np.clip(L - 1 - m0, 0, None)], 0.0)[:, :, None]      # [B, need0, 1]
-    for i, b in enumerate(blocks):
-        d, r = b["dilation"], b["base"]
-        n_out = need[i + 1]
-        convs = b["convs"]
-        jk = max(j for j, cv in enumerate(convs) if cv["k"] > 1)
-
-        def zero_below(a, stride):
-            m = np.arange(a.shape[1]) * stride
-            return np.where((L - 1 - d * m >= 0)[None, :, None], a, 0.0)
-
-        def padded(a, rows):
-            if a.shape[1] >= rows:
-                return a[:, :rows]
-            return np.concatenate([a, np.zeros((a.shape[0], rows - a.shape[1], a.shape[2]))], axis=1)
-
-        # rows of every conv's output: backwards from n_out strided outputs
-        rows = [0] * len(convs)
-        rows[-1] = n_out
-        for j in range(len(convs) - 1, 0, -1):
-            rows[j - 1] = (rows[j] - 1) * (r if j == jk else 1) + convs[j]["k"]
-        y, ystride = cur, 1
-        for j, cv in enumerate(convs):
-            w = cv["w"].astype(np.float64)                                  # [co, ci, k]; tap t reads m + t
-            k = cv["k"]
-            step = r if j == jk else 1
-            src = padded(y, (rows[j] - 1) * step + k)
-            out = np.zeros((B, rows[j], w.shape[0]))
-            for t in range(k):
-                out += src[:, t: t + (rows[j] - 1) * step + 1: step] @ w[:, :, k - 1 - t].T
-            ystride = r if j >= jk else 1
-            y = zero_below(np.maximum(out + cv["b"], 0.0), ystride)
-        xs = padded(cur, (n_out - 1) * r + 1)[:, ::r]
-        res = xs @ b["shortcut"][0].astype(np.float64).T + b["shortcut"][1] if b["shortcut"] is not None else xs
-        cur = zero_below(np.maximum(y + res, 0.0), r)
-    return cur[:, 0] @ fw.astype(np.float64).T + fb
 
 
 # ------------------------------------------------------------------------------------------------ CPU

@@ -12,6 +12,7 @@ import pytest
 from oracle import riser_oracle as ro
 from riser_amd import synth
 from riser_amd import tcn as T
+from tests.tcn_ref import bf16, x3_cone_forward, x3_matmul
 
 NAMES = ["tcn_k3_b2", "tcn_k5_b3", "bot_k3", "bot_k5"]
 
@@ -46,82 +47,20 @@ def _inputs(L):
     return np.stack([ro.mad_normalise(s) for s in sigs]).astype(np.float32)
 
 
-def bf16(v):
-    """fp32 -> the fp32 value of its bf16 rounding, to nearest even (what v_cvt_pk_bf16_f32 and the host packer do)"""
-    u = np.asarray(v, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    u = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32)
-    return u.view(np.float32)
-
-
-def split(v):
-    v = np.asarray(v, dtype=np.float32)
-    hi = bf16(v)
-    return hi.astype(np.float64), bf16(v - hi).astype(np.float64)
-
-
-def x3_matmul(a, w):
-    """a [..., K] fp32 @ w [K, N] fp32 in split precision: hi*hi + lo*hi + hi*lo, accumulated in float64, rounded to fp32"""
-    ah, al = split(a)
-    wh, wl = split(w)
-    return (ah @ wh + al @ wh + ah @ wl).astype(np.float32)
-
-
-def x3_cone_forward(blocks, fw, fb, x):
-    """the strided cone of csrc/tcn.hip / tcn_x3.hip (block i at positions L-1 - d_i m, zero below position 0, the convs up
-    to the last k-conv dense over m, that conv and what follows it at m = base m'), with every conv - the shortcut too - in
-    split precision and bias, ReLU and the residual add in fp32.  x: [B, L] fp32 (one length) -> logits float64 [B, 2]."""
-    x = np.asarray(x, dtype=np.float32)
-    B, L = x.shape
-    need = T.windows(blocks, L)
-    m0 = np.arange(need[0])
-    cur = np.where(L - 1 - m0 >= 0, x[:, np.clip(L - 1 - m0, 0, None)], 0.0).astype(np.float32)[:, :, None]
-    for i, b in enumerate(blocks):
-        d, r = b["dilation"], b["base"]
-        n_out = need[i + 1]
-        convs = b["convs"]
-        jk = max(j for j, cv in enumerate(convs) if cv["k"] > 1)
-
-        def zero_below(a, stride):
-            m = np.arange(a.shape[1]) * stride
-            return np.where((L - 1 - d * m >= 0)[None, :, None], a, np.float32(0)).astype(np.float32)
-
-        def padded(a, rows):
-            if a.shape[1] >= rows:
-                return a[:, :rows]
-            return np.concatenate([a, np.zeros((a.shape[0], rows - a.shape[1], a.shape[2]), np.float32)], axis=1)
-
-        rows = [0] * len(convs)
-        rows[-1] = n_out
-        for j in range(len(convs) - 1, 0, -1):
-            rows[j - 1] = (rows[j] - 1) * (r if j == jk else 1) + convs[j]["k"]
-        y = cur
-        for j, cv in enumerate(convs):
-            w = cv["w"]                                                     # [co, ci, k]; tap t reads m + t
-            k = cv["k"]
-            step = r if j == jk else 1
-            src = padded(y, (rows[j] - 1) * step + k)
-            # K tap-major: one GEMM over the concatenated taps, as the device runs it
-            a = np.concatenate([src[:, t: t + (rows[j] - 1) * step + 1: step] for t in range(k)], axis=2)
-            wk = np.concatenate([w[:, :, k - 1 - t].T for t in range(k)], axis=0)
-            out = x3_matmul(a, wk)
-            y = zero_below(np.maximum(out + cv["b"], np.float32(0)), r if j >= jk else 1)
-        xs = padded(cur, (n_out - 1) * r + 1)[:, ::r]
-        if b["shortcut"] is not None:
-            res = x3_matmul(xs, b["shortcut"][0].T) + b["shortcut"][1]
-        else:
-            res = xs
-        cur = zero_below(np.maximum(y + res, np.float32(0)), r)
-    return cur[:, 0].astype(np.float64) @ fw.astype(np.float64).T + fb
-
-
 # ------------------------------------------------------------------------------------------------ CPU
-def test_set_mode_abi_without_a_gpu():
+def test_set_mode_and_tile_plan_abi_without_a_gpu():
+    import ctypes as C
     from riser_amd import _native as nv
     lib = nv.lib()
-    assert lib.rs_version() == (2 << 16) | 7
+    assert lib.rs_version() == (2 << 16) | 8
     assert lib.rs_tcn_set_mode(None, nv.RS_BF16X3) == nv.RS_ERR_ARG
     assert b"rs_tcn_set_mode" in lib.rs_last_error()
     assert lib.rs_tcn_set_mode(None, nv.RS_F32) == nv.RS_ERR_ARG
+    # ABI 2.8: the tile-plan query refuses a null handle and leaves its outputs alone
+    t, nb, tiles = C.c_int(-7), C.c_int(-7), C.c_int(-7)
+    assert lib.rs_tcn_tile_plan(None, 0, 1, 1, C.byref(t), C.byref(nb), C.byref(tiles)) == nv.RS_ERR_ARG
+    assert b"rs_tcn_tile_plan" in lib.rs_last_error()
+    assert (t.value, nb.value, tiles.value) == (-7, -7, -7)
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -14,7 +14,7 @@ Reference entry points exercised:
   F3  SequencerControl.target                 riser/control.py:11-124 (fake client)
   F4  SignalProcessor.get_polyA_end           riser/preprocess.py:42-79
   F5  ResNet.forward                          riser/nets/resnet.py
-  F6  TCN.forward / TCNBot.forward            riser/nets/tcn.py, riser/nets/tcn_bot.py
+  F6  TCN.forward / TCNBot.forward            riser/nets/tcn.py, riser/nets/tcn_bot.py  (F6b: edge configs)
 """
 import json
 import logging
@@ -452,15 +452,16 @@ def tcn_lengths(rf):
     return (max(2, rf // 3), rf, rf + 1, 4097, 12000)
 
 
-def f6_tcn():
+def _tcn_golden(cfgs, seed, path, tag):
     """reference TCN / TCNBot (riser/nets/tcn.py, tcn_bot.py) in eval mode with randomised weights: weight_v, a weight_g
-    that is not ||v|| (weight_norm's initial value would hide folding bugs), non-zero biases, every shortcut (used or not)."""
+    that is not ||v|| (weight_norm's initial value would hide folding bugs), non-zero biases, every shortcut (used or not);
+    logits and probabilities at tcn_lengths(rf) of three synth reads."""
     from nets.tcn import TCN
     from nets.tcn_bot import TCNBot
     out = {}
-    rng = np.random.default_rng(4242)
-    torch.manual_seed(4242)
-    for name, (bot, cfg) in TCN_CFGS.items():
+    rng = np.random.default_rng(seed)
+    torch.manual_seed(seed)
+    for name, (bot, cfg) in cfgs.items():
         net = (TCNBot if bot else TCN)(types.SimpleNamespace(**cfg))
         sd = net.state_dict()
         new = {}
@@ -490,8 +491,29 @@ def f6_tcn():
             out[f"{name}.sd.{k}"] = v.numpy()
         out[f"{name}.cfg"] = np.array(json.dumps(dict(cfg, model="tcn-bot" if bot else "tcn", rf=int(rf),
                                                       lengths=[int(v) for v in lens])))
-        print("F6:", name, "RF", rf, out[f"{name}.L4097.probs"][:, 1])
-    np.savez_compressed(os.path.join(OUT, "tcn.npz"), **out)
+        print(f"{tag}:", name, "RF", rf, out[f"{name}.L4097.probs"][:, 1])
+    np.savez_compressed(os.path.join(OUT, path), **out)
+
+
+def f6_tcn():
+    _tcn_golden(TCN_CFGS, 4242, "tcn.npz", "F6")
+
+
+TCN_EDGE_CFGS = {
+    # the edges of the device's TCN program the configs above leave out (tests/test_tcn_shapes.py sweeps them on the GPU)
+    "tcn_f1_k2": (False, dict(in_channels=1, n_filters=1, kernel=2, dilation=1, n_layers=3, dropout=0.2, n_classes=2)),
+    "tcn_k5_l1": (False, dict(in_channels=1, n_filters=20, kernel=5, dilation=3, n_layers=1, dropout=0.2, n_classes=2)),
+    "tcn_k2_b4": (False, dict(in_channels=1, n_filters=13, kernel=2, dilation=4, n_layers=7, dropout=0.2, n_classes=2)),
+    "tcn_f68": (False, dict(in_channels=1, n_filters=68, kernel=3, dilation=2, n_layers=2, dropout=0.2, n_classes=2)),
+    "bot_f4": (True, dict(in_channels=1, n_filters=4, kernel=3, dilation=2, n_layers=4, dropout=0.2, n_classes=2)),
+    "bot_f22_k2": (True, dict(in_channels=1, n_filters=22, kernel=2, dilation=2, n_layers=6, dropout=0.2, n_classes=2)),
+}
+
+
+def f6b_tcn_edges():
+    """F6 at the edges: one filter (identity residual in block 0), one layer, k 2, base 4, a partial second 64-column
+    group (68 filters), TCNBot mid widths 1 and 5"""
+    _tcn_golden(TCN_EDGE_CFGS, 4243, "tcn_edges.npz", "F6b")
 
 
 if __name__ == "__main__":
@@ -518,3 +540,5 @@ if __name__ == "__main__":
         f5_resnet()
     if "f6" in which:
         f6_tcn()
+    if "f6b" in which:
+        f6b_tcn_edges()
