@@ -407,6 +407,55 @@ RS_API int rs_tcn_set_mode(rs_tcn* m, int dtype);
  * no launch.  A bad argument, or a block too wide for one tile of LDS (what the forward refuses), returns RS_ERR_ARG. */
 RS_API int rs_tcn_tile_plan(const rs_tcn* m, int block, int B, int ld, int* T, int* nb, int* tiles_pos);
 
+/*
+ * CNN-RNN (added after ABI 2.8; rs_version is unchanged): riser/nets/cnn_rnn.py's ConvRecNet, loaded by Model for
+ * `model: cnn-rnn`.  The conv front is n_conv x [valid Conv1d(c_in, c_out, k) + bias -> MaxPool1d(2, 2) -> ReLU]: a read of
+ * L samples has L_{i+1} = (L_i - k_i + 1) // 2 and T = L_n recurrent steps.  The recurrent stack is a flat list of LSTM / GRU
+ * layers (the reference nests n_rec_layers modules of n_rec_layers layers each: n_rec_layers^2 layers, a ReLU on the output
+ * sequence after each module, `relu_after`); the head is Linear(out_dim -> 2) on the last step + softmax.  Gate order as
+ * torch stores it: LSTM i, f, g, o; GRU r, z, n with n = tanh(W_in x + b_in + r * (W_hn h + b_hn)).  Zero initial state.
+ * fp32 throughout on the f32-input MFMA (csrc/crnn.hip): one fused launch per conv layer, per recurrent layer one input
+ * projection GEMM per direction and one persistent launch that loops over t (both directions in it).  The last layer's
+ * output sequence is never written, and its backward direction runs one step (the head reads its first step).
+ */
+typedef struct rs_crnn_conv {
+    int32_t c_in, c_out, k;
+    int32_t reserved;
+    const float* w;         /* HOST fp32 [c_out, c_in, k] */
+    const float* b;         /* HOST fp32 [c_out] */
+} rs_crnn_conv;
+typedef struct rs_crnn_layer {
+    int32_t cell;           /* 0 LSTM, 1 GRU */
+    int32_t in_dim;         /* the last conv's c_out, or the previous layer's hidden x (2 if bidirectional) */
+    int32_t hidden;         /* 1..320 */
+    int32_t bidirectional;  /* 0 / 1: index 1 of the arrays below is the backward direction (torch's `_reverse`) */
+    int32_t relu_after;     /* 1: ReLU on this layer's output (the last layer of a module); the last layer always has it */
+    int32_t reserved;
+    const float* w_ih[2];   /* HOST fp32 [gates * hidden, in_dim] */
+    const float* w_hh[2];   /* HOST fp32 [gates * hidden, hidden] */
+    const float* b_ih[2];   /* HOST fp32 [gates * hidden] */
+    const float* b_hh[2];
+} rs_crnn_layer;
+typedef struct rs_crnn rs_crnn;
+RS_API int rs_crnn_create(const rs_crnn_conv* convs, int n_conv, const rs_crnn_layer* layers, int n_layers,
+                          const float* fc_w /* [2, out_dim] */, const float* fc_b, int out_dim, int device, rs_crnn** out);
+RS_API int rs_crnn_destroy(rs_crnn* m);
+/* shortest read the reference can run (shorter: its conv or max_pool raises); a null handle returns RS_ERR_ARG */
+RS_API int rs_crnn_min_length(const rs_crnn* m);
+/* recurrent steps T of a read of `len` samples (0 below the minimum); a null handle or len < 0 returns RS_ERR_ARG */
+RS_API int rs_crnn_steps(const rs_crnn* m, int len);
+/* 0 for a null handle, B < 1 or ld below the minimum */
+RS_API size_t rs_crnn_workspace_bytes(const rs_crnn* m, int B, int ld);
+/* largest B whose activation buffers each stay inside the 2 GiB buffer window for reads of pitch ld; callers split bigger
+ * batches.  0 for a null handle or ld below the minimum */
+RS_API int rs_crnn_max_batch(const rs_crnn* m, int ld);
+/* Read b is d_x[b * ld .. b * ld + d_len[b]) (a larger d_len is read as ld) with its own T_b steps; the reads' recurrences
+ * are aligned to end on the same step and a read gets the bits it gets alone, whatever the batch or ld.  ld below the
+ * minimum returns RS_ERR_LENGTH; a read whose d_len is below it gets NaN probabilities (check lengths on the host).
+ * d_logits may be null. */
+RS_API int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x /* fp32 [B, ld] */, const int32_t* d_len, int B, int ld,
+                                  void* d_ws, size_t ws_bytes, float* d_probs /* [B, 2] */, float* d_logits, void* stream);
+
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag

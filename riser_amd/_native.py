@@ -27,6 +27,8 @@ SYMBOLS = (
     "rs_seqnet_create", "rs_seqnet_destroy", "rs_seqnet_workspace_bytes", "rs_seqnet_forward", "rs_seqnet_set_mode", "rs_seqnet_ragged_ok", "rs_seqnet_forward_ragged", "rs_seqnet_max_batch",
     "rs_tcn_create", "rs_tcn_destroy", "rs_tcn_receptive_field", "rs_tcn_workspace_bytes", "rs_tcn_max_batch", "rs_tcn_forward_ragged", "rs_tcn_set_mode",
     "rs_tcn_tile_plan",
+    "rs_crnn_create", "rs_crnn_destroy", "rs_crnn_min_length", "rs_crnn_steps", "rs_crnn_workspace_bytes", "rs_crnn_max_batch",
+    "rs_crnn_forward_ragged",
 )
 
 
@@ -134,6 +136,20 @@ def lib():
     L.rs_tcn_set_mode.argtypes = [vp, i32]
     L.rs_tcn_tile_plan.restype = i32
     L.rs_tcn_tile_plan.argtypes = [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.rs_crnn_create.restype = i32
+    L.rs_crnn_create.argtypes = [vp, i32, vp, i32, vp, vp, i32, i32, C.POINTER(vp)]
+    L.rs_crnn_destroy.restype = i32
+    L.rs_crnn_destroy.argtypes = [vp]
+    L.rs_crnn_min_length.restype = i32
+    L.rs_crnn_min_length.argtypes = [vp]
+    L.rs_crnn_steps.restype = i32
+    L.rs_crnn_steps.argtypes = [vp, i32]
+    L.rs_crnn_workspace_bytes.restype = sz
+    L.rs_crnn_workspace_bytes.argtypes = [vp, i32, i32]
+    L.rs_crnn_max_batch.restype = i32
+    L.rs_crnn_max_batch.argtypes = [vp, i32]
+    L.rs_crnn_forward_ragged.restype = i32
+    L.rs_crnn_forward_ragged.argtypes = [vp, vp, vp, i32, i32, vp, sz, vp, vp, vp]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32

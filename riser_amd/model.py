@@ -76,6 +76,12 @@ class Model:
         if logger is not None:
             logger.info('Using %s device', self.device)
         kind = getattr(config, "model", None)
+        if kind == "cnn-rnn" or (kind is None and not hasattr(config, "cnn") and hasattr(config, "cnn_rnn")):
+            # `config.cnn_rnn` (riser/nets/cnn_rnn.py:7-33, ConvRecNet): conv front + stacked LSTM / GRU (csrc/crnn.hip).
+            # The reference's train.py has no branch for it; `model: cnn-rnn`, or a config with a `cnn_rnn` section and
+            # neither `model` nor `cnn`, selects it here
+            self._init_crnn(state, config.cnn_rnn, dtype)
+            return
         is_resnet = kind == "resnet" or (not hasattr(config, "cnn") and hasattr(config, "resnet"))
         if not is_resnet and (kind == "tcn-bot" or (kind != "tcn" and not hasattr(config, "cnn") and hasattr(config, "tcnbot"))):
             # `config.tcnbot` (riser/nets/tcn_bot.py:63-85) or `config.tcn` (riser/nets/tcn.py:62-82), what riser/train.py:175-182
@@ -312,6 +318,21 @@ class Model:
         self.dtype = self._seq.dtype
         self._ws = Workspace(self.device)
         self.min_length = 1                 # causal convs: any read of one sample or more has a last position
+
+    def _init_crnn(self, state, cc, dtype: str):
+        from .crnn import CRNNNet, build_crnn_program
+        if dtype not in ("f32w", "f32"):
+            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) only")
+        sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
+        prog = build_crnn_program(sd, cc)
+        self.classifier, self._fc_positions = "gap_fc", 0
+        self.channels = [int(cv["w"].shape[0]) for cv in prog["convs"]]
+        self.n_layers = len(self.channels)
+        self._keep, self._h, self.model = [], None, self
+        self._seq = CRNNNet(prog, device=self.device, dtype=dtype)
+        self.dtype = self._seq.dtype
+        self._ws = Workspace(self.device)
+        self.min_length = self._seq.min_length      # shorter: the reference's conv or max_pool raises
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

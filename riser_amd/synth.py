@@ -375,3 +375,56 @@ def make_tcn_state_dict(seed: int, cfg: dict = None, bottleneck: bool = False) -
     sd["linear.weight"] = (u(cfg["n_classes"] * nf) * np.float32(0.3)).reshape(cfg["n_classes"], nf).astype(np.float32)
     sd["linear.bias"] = (u(cfg["n_classes"]) * np.float32(0.1)).astype(np.float32)
     return sd
+
+
+# riser/nets/cnn_rnn.py (ConvRecNet): 4 conv layers, then n_rec_layers modules of n_rec_layers bidirectional layers each
+CRNN_BENCH_CFG = dict(n_conv_layers=4, channels=[32, 64, 128, 128], kernels=[9, 7, 5, 3], cell="lstm", hidden=128,
+                      n_rec_layers=2, bidirectional=True, dropout=0.2, n_classes=2)
+CRNN_GRU_BENCH_CFG = dict(CRNN_BENCH_CFG, cell="gru")
+
+
+def make_crnn_state_dict(seed: int, cfg: dict = None, gain: float = 1.0) -> dict:
+    """Reference-format ConvRecNet state dict (riser/nets/cnn_rnn.py: conv_layers.{i}.0.*, rec_layers.{m}.{weight,bias}_
+    {ih,hh}_l{j}[_reverse], linear.*) from the integer hash.  Conv weights have unit gain (uniform with variance 1 / fan_in),
+    input-to-gate weights unit gain, hidden-to-gate weights torch's own range 1 / sqrt(hidden): activations stay O(1).
+    `gain` scales the hidden-to-gate and head weights (the golden fixtures use 2, so that a deep stack still moves the
+    logits)."""
+    cfg = cfg or CRNN_BENCH_CFG
+    sd, stream = {}, [0]
+
+    def u(n):
+        stream[0] += 1
+        return uniform_pm1(seed, 8000 + stream[0], n)
+
+    c_in = 1
+    for i in range(cfg["n_conv_layers"]):
+        co, k = cfg["channels"][i], cfg["kernels"][i]
+        sd[f"conv_layers.{i}.0.weight"] = (u(co * c_in * k) * np.float32(np.sqrt(3.0 / (c_in * k)))).reshape(co, c_in, k).astype(np.float32)
+        sd[f"conv_layers.{i}.0.bias"] = (u(co) * np.float32(0.05)).astype(np.float32)
+        c_in = co
+    H, n = cfg["hidden"], cfg["n_rec_layers"]
+    g = (4 if cfg["cell"] == "lstm" else 3) * H
+    ndir = 2 if cfg["bidirectional"] else 1
+    for m in range(n):
+        for j in range(n):
+            in_dim = (cfg["channels"][-1] if m == 0 else H * ndir) if j == 0 else H * ndir
+            for sfx in ("", "_reverse")[:ndir]:
+                pre, post = f"rec_layers.{m}.", f"_l{j}{sfx}"
+                sd[pre + "weight_ih" + post] = (u(g * in_dim) * np.float32(np.sqrt(3.0 / in_dim))).reshape(g, in_dim).astype(np.float32)
+                sd[pre + "weight_hh" + post] = (u(g * H) * np.float32(gain / np.sqrt(H))).reshape(g, H).astype(np.float32)
+                sd[pre + "bias_ih" + post] = (u(g) * np.float32(0.1)).astype(np.float32)
+                sd[pre + "bias_hh" + post] = (u(g) * np.float32(0.1)).astype(np.float32)
+    sd["linear.weight"] = (u(2 * H * ndir) * np.float32(0.3 * gain)).reshape(2, H * ndir).astype(np.float32)
+    sd["linear.bias"] = (u(2) * np.float32(0.1)).astype(np.float32)
+    return sd
+
+
+def state_dict_sha16(sd: dict) -> str:
+    """sha256[:16] over a state dict's keys (sorted), dtypes, shapes and bytes: pins a generated state dict to its fixture"""
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(sd):
+        v = np.ascontiguousarray(sd[k])
+        h.update(f"{k}|{v.dtype.str}|{v.shape}|".encode())
+        h.update(v.tobytes())
+    return h.hexdigest()[:16]

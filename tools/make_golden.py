@@ -15,6 +15,7 @@ Reference entry points exercised:
   F4  SignalProcessor.get_polyA_end           riser/preprocess.py:42-79
   F5  ResNet.forward                          riser/nets/resnet.py
   F6  TCN.forward / TCNBot.forward            riser/nets/tcn.py, riser/nets/tcn_bot.py  (F6b: edge configs)
+  F7  ConvRecNet.forward                      riser/nets/cnn_rnn.py
 """
 import json
 import logging
@@ -516,6 +517,85 @@ def f6b_tcn_edges():
     _tcn_golden(TCN_EDGE_CFGS, 4243, "tcn_edges.npz", "F6b")
 
 
+CRNN_CFGS = {
+    # LSTM and GRU, uni- and bidirectional, n_rec_layers 1 / 2 / 3 (1, 4 and 9 stacked layers), an even conv kernel, hidden
+    # sizes off the multiples of 16 (17, 20) and above 128 (130: W_hh not register-resident on the device), one conv layer
+    "lstm_bi_r2": dict(n_conv_layers=3, channels=[8, 16, 16], kernels=[5, 4, 3], cell="lstm", hidden=20, n_rec_layers=2,
+                       bidirectional=True, dropout=0.2, n_classes=2),
+    "gru_bi_r1_c1": dict(n_conv_layers=1, channels=[12], kernels=[6], cell="gru", hidden=17, n_rec_layers=1,
+                         bidirectional=True, dropout=0.2, n_classes=2),
+    "lstm_uni_r3": dict(n_conv_layers=2, channels=[16, 24], kernels=[7, 3], cell="lstm", hidden=24, n_rec_layers=3,
+                        bidirectional=False, dropout=0.2, n_classes=2),
+    "gru_uni_r2_h130": dict(n_conv_layers=2, channels=[8, 32], kernels=[3, 3], cell="gru", hidden=130, n_rec_layers=2,
+                            bidirectional=False, dropout=0.2, n_classes=2),
+    "lstm_bi_h130": dict(n_conv_layers=2, channels=[8, 16], kernels=[4, 5], cell="lstm", hidden=130, n_rec_layers=1,
+                         bidirectional=True, dropout=0.2, n_classes=2),
+    "gru_bi_r2": dict(n_conv_layers=3, channels=[8, 16, 32], kernels=[3, 5, 3], cell="gru", hidden=32, n_rec_layers=2,
+                      bidirectional=True, dropout=0.2, n_classes=2),
+}
+
+
+CRNN_GAIN = 2.0        # synth.make_crnn_state_dict's gain for the fixture: every mutant of tests/crnn_ref.py shows
+
+
+def crnn_min_length(kernels):
+    need = 1
+    for k in reversed(kernels):
+        need = 2 * need + k - 1
+    return need
+
+
+def crnn_odd_pool_length(kernels, start):
+    """the shortest length from `start` on where some max_pool drops an odd last sample"""
+    L0 = start
+    while True:
+        L, odd = L0, False
+        for k in kernels:
+            odd |= (L - k + 1) % 2 == 1
+            L = (L - k + 1) // 2
+        if odd:
+            return L0
+        L0 += 1
+
+
+def crnn_lengths(kernels):
+    mn = crnn_min_length(kernels)
+    return (mn, mn + 1, crnn_odd_pool_length(kernels, mn + 2), 4097, 12000)
+
+
+def f7_crnn():
+    """reference ConvRecNet (riser/nets/cnn_rnn.py) in eval mode with random weights and non-zero biases (b_ih and b_hh
+    both); logits and probabilities at crnn_lengths of three synth reads.  The weights are not stored: they are
+    synth.make_crnn_state_dict(seed, cfg) (the integer hash, the same on every platform), loaded strictly into the
+    reference's own module, and the cfg records the seed and synth.state_dict_sha16 of them so that a test can rebuild them
+    and tell when the generator has drifted."""
+    from nets.cnn_rnn import ConvRecNet
+    out = {}
+    torch.manual_seed(4711)
+    for n, (name, cfg) in enumerate(CRNN_CFGS.items()):
+        net = ConvRecNet(types.SimpleNamespace(**cfg))
+        seed = 4711 + n
+        sd = synth.make_crnn_state_dict(seed, cfg, gain=CRNN_GAIN)
+        new = {k: torch.from_numpy(v) for k, v in sd.items()}
+        net.load_state_dict(new, strict=True)                          # the reference's own key set and shapes
+        net.eval()
+        lens = crnn_lengths(cfg["kernels"][: cfg["n_conv_layers"]])
+        proc = SignalProcessor(Kit.create_from_version("RNA004"))
+        for L in lens:
+            sigs = synth.make_signals(SIG_SEED, 3, L, first_read=60)
+            x = np.stack([proc.mad_normalise(s.copy()) for s in sigs]).astype(np.float32)
+            with torch.no_grad():
+                logits = net(torch.from_numpy(x))
+                probs = torch.softmax(logits, dim=1)
+            out[f"{name}.L{L}.logits"] = logits.numpy()
+            out[f"{name}.L{L}.probs"] = probs.numpy()
+        out[f"{name}.cfg"] = np.array(json.dumps(dict(cfg, model="cnn-rnn", min_length=int(lens[0]),
+                                                      lengths=[int(v) for v in lens], seed=seed, gain=CRNN_GAIN,
+                                                      sd_sha16=synth.state_dict_sha16(sd))))
+        print("F7:", name, "min", lens[0], out[f"{name}.L4097.probs"][:, 1])
+    np.savez_compressed(os.path.join(OUT, "crnn.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -542,3 +622,5 @@ if __name__ == "__main__":
         f6_tcn()
     if "f6b" in which:
         f6b_tcn_edges()
+    if "f7" in which:
+        f7_crnn()
