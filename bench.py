@@ -2,7 +2,7 @@
 """bench.py - chunks/s of the squiggle-classification hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config rna004_b512|promethion|progressive]
-                    [--dtype f32|f32_direct|bf16|f16|bf16x3|f16x3] [--dump-outputs DIR]
+                    [--dtype f32|f32_direct|bf16|f16|bf16x3|f16x3] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic reads already resident in HBM:
 MAD-normalise + 12-layer ConvNet forward + softmax, through the C ABI.
@@ -41,6 +41,12 @@ Prints ONE JSON line on rank 0.  Extra objects:
   cpu_baseline  the oracle's torch-CPU port timed on this box's host cores over a bounded sample, best of a sweep
                 over thread counts (rank 0, N = 1 only)
   control_loop  scripted 512-channel ReadUntil batches through the batched SequencerControl: p50 / p99 per batch
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; its `roofline` is what the
+events inside the timed steps give.  --full adds everything that takes work of its own after the timed steps: the
+per-launch pass (roofline.layers, the stage times), the batch latency, the sustained and host-fed figures, the variants,
+the control loop, the CPU baseline and the verbose detail file (--no-latency / --no-variants / --no-control-loop /
+--no-cpu-baseline drop single parts of it).
 """
 import argparse
 import json
@@ -108,6 +114,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-control-loop", action="store_true", help="skip the ReadUntil replay")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements after the timed steps (per-launch pass, latency, variants, control loop, "
+                         "CPU baseline) and the detail file")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # CPU rehearsal of the rank plumbing (tests)
     ap.add_argument("--stub-fail-rank", type=int, default=None, help=argparse.SUPPRESS)   # tests: this rank dies before the rendezvous
     args = ap.parse_args(argv)
@@ -321,9 +330,10 @@ def traffic_object(args, model, wl):
             "source": os.path.relpath(path, ROOT), "profiled_csrc_sha16": stamp, "kernels_match_tree": fresh}
 
 
-def roofline_object(args, model, wl, conv_ms_total, conv_calls, stage_ms, detail_calls):
+def roofline_object(args, model, wl, conv_ms_total, conv_calls, launches=None):
     """conv stack = layers 1..n-1.  conv_ms_total: HIP-event time of the conv stack summed over `conv_calls` library
-    calls of the timed region; stage_ms / detail_calls: the per-launch pass."""
+    calls of the timed region; launches: (stage_ms, detail_calls) of the per-launch pass (--full), or None: no per-layer
+    and per-stage figures."""
     lib_dtype = LIB_DTYPE.get(args.dtype, args.dtype)
     L = args.chunk
     nl = model.n_layers
@@ -337,14 +347,17 @@ def roofline_object(args, model, wl, conv_ms_total, conv_calls, stage_ms, detail
     conv_ms_step = conv_ms_total / steps_timed if steps_timed else 0.0
     info = model.layer_info()
     passes = MFMA_PASSES.get(args.dtype, 1)
+    stage_ms, detail_calls = launches if launches is not None else (None, 0)
     per_layer, executed_step = [], 0.0
     for i in range(1, nl):
-        ms = float(stage_ms[1 + i]) / max(detail_calls, 1)                       # per library call
         U = info[i]["block_samples"]                                             # packed layout: len // U + 1 blocks per read,
         blocks_step = int((lens.astype(np.int64) // U + 1).sum())               # finer blocks below the last three layers
         rows = blocks_step * -(-(U >> i) // info[i]["gemm_row_div"])              # GEMM rows of a step
         ex = 2.0 * rows * info[i]["n_pad"] * info[i]["k_pad"] * passes
         executed_step += ex
+        if stage_ms is None:
+            continue
+        ms = float(stage_ms[1 + i]) / max(detail_calls, 1)                       # per library call
         fl_call = layer_flop_step[i] / wl.calls_per_step
         per_layer.append({"layer": i, "ms": round(ms, 4),
                           "algorithmic_tflops": round(fl_call / (ms * 1e-3) / 1e12, 2) if ms > 0 else None,
@@ -359,11 +372,10 @@ def roofline_object(args, model, wl, conv_ms_total, conv_calls, stage_ms, detail
     kname = {"f32w": "conv_stream_f32_kernel / conv_wino_kernel / conv_wino4_kernel (Winograd F(2,3) layers %s, F(4,3) "
                      "layers %s, f32-input MFMA)" % (",".join(f23), ",".join(f43)),
              "f32": "conv_f32_kernel (direct, f32-input MFMA)"}.get(lib_dtype, "16-bit MFMA conv kernels (%s)" % lib_dtype)
-    conv_ms_detail = float(stage_ms[2:2 + nl - 1].sum()) / max(detail_calls, 1)
     overlap = ({"streams_note": f"{args.streams} sub-batches in flight: the per-call HIP-event times overlap, so `achieved` / `frac` "
                                 "(FLOPs over the SUM of those times) understate the pipe's share; use --streams 1 for the roofline"}
                if getattr(args, "streams", 1) > 1 else {})
-    return {**overlap, "bound": "mfma", "kernel": kname + f", {nl - 1} launches per call, layers 1-{nl - 1}",
+    roof = {**overlap, "bound": "mfma", "kernel": kname + f", {nl - 1} launches per call, layers 1-{nl - 1}",
             "achieved": round(exe_tf, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(exe_tf / peak, 4),
             # counters of OTHER kernel sources are not this tree's traffic: null, the stale figure stays in traffic_detail
             "traffic": traffic["bytes_per_launch"] if traffic and traffic["kernels_match_tree"] else None,
@@ -381,13 +393,17 @@ def roofline_object(args, model, wl, conv_ms_total, conv_calls, stage_ms, detail
             "conv_stack_ms_per_call": round(conv_ms_step / wl.calls_per_step, 4) if wl.calls_per_step else None,
             "reads_per_call": round(reads_per_call, 1),
             "timing_note": "achieved / avg_launch_ms: HIP events around the conv stack inside the timed steps; stage_ms and "
-                           "layers[]: a separate pass with one event per launch (each event adds ~4.5 us of stream time)",
-            "conv_stack_ms_per_launch_events": round(conv_ms_detail, 4),
-            "stage_ms": {"normalise": round(float(stage_ms[0]) / max(detail_calls, 1), 4),
-                         "conv0": round(float(stage_ms[1]) / max(detail_calls, 1), 4),
-                         "conv1_11": round(conv_ms_detail, 4),
-                         "head": round(float(stage_ms[nl + 1]) / max(detail_calls, 1), 4)},
-            "layers": per_layer}
+                           "layers[] (--full): a separate pass with one event per launch (each event adds ~4.5 us of stream "
+                           "time)"}
+    if stage_ms is not None:
+        conv_ms_detail = float(stage_ms[2:2 + nl - 1].sum()) / max(detail_calls, 1)
+        roof.update({"conv_stack_ms_per_launch_events": round(conv_ms_detail, 4),
+                     "stage_ms": {"normalise": round(float(stage_ms[0]) / max(detail_calls, 1), 4),
+                                  "conv0": round(float(stage_ms[1]) / max(detail_calls, 1), 4),
+                                  "conv1_11": round(conv_ms_detail, 4),
+                                  "head": round(float(stage_ms[nl + 1]) / max(detail_calls, 1), 4)},
+                     "layers": per_layer})
+    return roof
 
 
 def _longest_run(sig: np.ndarray) -> int:
@@ -894,18 +910,21 @@ def main(argv=None):
     total_chunks = rdist.reduce_scalar(wl.reads_per_step * args.steps, "sum", device)
     conv_ms_total = float(coarse_ms[model.n_layers])                       # layers 1..n-1 over the timed region
 
+    # every pass from here on is --full only: a plain run goes straight to its line
     # per-launch detail (not timed): one event after every kernel
-    model.profile(True)
-    for _ in range(max(5, min(args.steps, 20)) if args.config != "promethion" else 1):
-        step()
-    torch.cuda.synchronize(device)
-    stage_ms, detail_calls = model.profile_read()
-    model.profile(False)
+    launches = None
+    if args.full:
+        model.profile(True)
+        for _ in range(max(5, min(args.steps, 20)) if args.config != "promethion" else 1):
+            step()
+        torch.cuda.synchronize(device)
+        launches = model.profile_read()
+        model.profile(False)
 
     # ---- per-batch latency incl. H2D of the int16 batch and D2H of the probabilities -----------
     p50 = p99 = 0.0
     n_lat = 0
-    if not args.no_latency and args.config != "promethion":
+    if args.full and not args.no_latency and args.config != "promethion":
         host_sig = torch.from_numpy(np.ascontiguousarray(wl.sample_sigs.reshape(-1))).pin_memory()
         host_probs = torch.empty((B, 2), dtype=torch.float32).pin_memory()
         lat = []
@@ -920,7 +939,8 @@ def main(argv=None):
         lat_ms = np.asarray(lat) * 1e3
         n_lat = len(lat)
         p50, p99 = float(np.percentile(lat_ms, 50)), float(np.percentile(lat_ms, 99))
-    p99 = rdist.reduce_scalar(p99, "max", device)
+    if args.full:
+        p99 = rdist.reduce_scalar(p99, "max", device)
 
     if rank != 0:
         rdist.finalize()
@@ -938,15 +958,17 @@ def main(argv=None):
                    "conv_algorithm": {"f32w": "winograd_f23_f43_fp32", "f32": "direct_fp32"}.get(lib_dtype, "direct_" + lib_dtype),
                    "batch_per_call": B, "reads_per_gpu_per_step": wl.reads_per_step, "chunk_samples": L,
                    "sharding": "reads by id across GPUs, no collectives"},
-        "p50_batch_latency_ms": round(p50, 3), "p99_batch_latency_ms": round(p99, 3), "latency_samples": n_lat,
-        "latency_note": f"host wall time per {B}-read batch incl. H2D of int16 signals from pinned memory and D2H of "
-                        f"probabilities; {LAT_SAMPLES} batches after {LAT_WARMUP} warm-up (kernel loop + PCIe; the ReadUntil "
-                        "loop's own latency is control_loop)",
-        "roofline": roofline_object(args, model, wl, conv_ms_total, conv_calls, stage_ms, detail_calls),
+        "roofline": roofline_object(args, model, wl, conv_ms_total, conv_calls, launches),
     }
+    if args.full:
+        detail.update({
+            "p50_batch_latency_ms": round(p50, 3), "p99_batch_latency_ms": round(p99, 3), "latency_samples": n_lat,
+            "latency_note": f"host wall time per {B}-read batch incl. H2D of int16 signals from pinned memory and D2H of "
+                            f"probabilities; {LAT_SAMPLES} batches after {LAT_WARMUP} warm-up (kernel loop + PCIe; the ReadUntil "
+                            "loop's own latency is control_loop)"})
 
     detail["per_rank"] = per_rank
-    single = world == 1 and args.config == "rna004_b512"
+    single = args.full and world == 1 and args.config == "rna004_b512"
     # ---- the same step over a window of seconds, and fed from pinned host memory ----
     if single and not args.no_latency:
         detail["sustained"] = sustained_object(step, device, B, value)
@@ -960,9 +982,10 @@ def main(argv=None):
     if single and not args.no_cpu_baseline:
         detail["cpu_baseline"] = cpu_baseline_object(args, wl.sample_sigs)
     line = compact_line(detail, args, model, wl)
-    path = write_detail(detail, args)
-    if path:
-        line["detail_file"] = path
+    if args.full:
+        path = write_detail(detail, args)
+        if path:
+            line["detail_file"] = path
     print(json.dumps(line, separators=(",", ":")), flush=True)
     rdist.finalize()
     return 0
@@ -1042,11 +1065,12 @@ def compact_line(detail, args, model, wl):
     line["config"] = {"workload": c["workload"], "name": c["name"], "conv_algorithm": c["conv_algorithm"],
                       "batch_per_call": c["batch_per_call"], "chunk_samples": c["chunk_samples"], "sharding": c["sharding"]}
     for k in ("p50_batch_latency_ms", "p99_batch_latency_ms", "latency_samples"):
-        line[k] = detail[k]
+        if k in detail:                                       # --full
+            line[k] = detail[k]
     if detail.get("per_rank") and detail["n_gpus"] > 1:
         line["per_rank"] = detail["per_rank"]
     r = detail["roofline"]
-    layers = [x for x in r["layers"] if x["ms"]]
+    layers = [x for x in r.get("layers", []) if x["ms"]]
     dom = max(layers, key=lambda x: x["ms"]) if layers else None
     # the order matters: the driver's record keeps the head of this object (round 5's `parsed` ended behind slowest_layer_*), so
     # what the round is judged on comes first
@@ -1084,10 +1108,11 @@ def compact_line(detail, args, model, wl):
                  "achieved_is": "executed MFMA FLOPs (padded, Winograd-reduced) / HIP-event time of conv layers 1-11",
                  "algorithmic_tflops": r["algorithmic_tflops"],
                  "algorithmic_frac": round(r["algorithmic_tflops"] / r["peak"], 4),
-                 "avg_launch_ms": r["avg_launch_ms"], "conv_stack_ms_per_call": r["conv_stack_ms_per_call"],
-                 "normalise_ms": r["stage_ms"]["normalise"], "head_ms": r["stage_ms"]["head"],
-                 "p50_batch_latency_ms": detail["p50_batch_latency_ms"], "p99_batch_latency_ms": detail["p99_batch_latency_ms"],
-                 "latency_window_s": 1.0})
+                 "avg_launch_ms": r["avg_launch_ms"], "conv_stack_ms_per_call": r["conv_stack_ms_per_call"]})
+    if "stage_ms" in r:                                            # --full: the per-launch pass and the latency loop
+        roof.update({"normalise_ms": r["stage_ms"]["normalise"], "head_ms": r["stage_ms"]["head"],
+                     "p50_batch_latency_ms": detail["p50_batch_latency_ms"],
+                     "p99_batch_latency_ms": detail["p99_batch_latency_ms"], "latency_window_s": 1.0})
     if dom:
         roof.update({"slowest_layer": dom["layer"], "slowest_layer_ms": dom["ms"],
                      "slowest_layer_executed_tflops": dom["executed_tflops"],

@@ -265,6 +265,31 @@ def test_bench_dump_outputs_are_what_the_timed_step_returned(dev, tmp_path):
     assert set(rejected.tolist()) <= set(finished.tolist()) <= set(range(1, 65))
 
 
+def test_bench_plain_run_prints_the_headline_and_full_adds_the_side_passes():
+    """a plain `bench.py` prints the headline and the roofline of the HIP events inside the timed steps, nothing that needs
+    work after them; `--full` adds the per-launch pass (slowest layer, stage times), the latency fields and the detail file"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    base = ["--gpus", "1", "--steps", "3", "--warmup", "1"]
+    quiet = ["--no-latency", "--no-variants", "--no-control-loop", "--no-cpu-baseline"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", *quiet])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *base, *extra], cwd=ROOT, capture_output=True,
+                           text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        got = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1
+        lines[name] = json.loads(got[0])
+    for out in lines.values():
+        assert out["unit"] == "chunks/s" and out["dtype"] == "f32" and out["higher_is_better"] is True
+        assert out["steps"] == 3 and abs(out["value"] - 512 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-3
+        assert out["roofline"]["achieved"] > 0 and 0 < out["roofline"]["frac"] < 1
+    plain, full = lines["plain"], lines["full"]
+    assert not {"p50_batch_latency_ms", "latency_samples", "detail_file", "cpu_baseline", "control_loop"} & set(plain)
+    assert not {"slowest_layer", "normalise_ms", "sustained_value"} & set(plain["roofline"])
+    assert full["latency_samples"] == 0 and "detail_file" in full
+    assert full["roofline"]["slowest_layer"] in range(1, 12) and full["roofline"]["normalise_ms"] > 0
+
+
 @pytest.mark.parametrize("dtype", ["f32w", "f32", "bf16x3"])
 def test_length_mismatch_is_contained_on_every_path(dev, dtype):
     """host lengths that disagree with the device's - above AND below - on the fused path of every dtype
