@@ -353,6 +353,32 @@ RS_API int rs_seqnet_max_batch(const rs_seqnet* m, int L);
 RS_API int rs_seqnet_ragged_ok(const rs_seqnet* m);
 RS_API int rs_seqnet_forward_ragged(rs_seqnet* m, const float* d_x /* fp32 [B, ld] */, const int32_t* d_len, int B, int ld, void* d_ws,
                              size_t ws_bytes, float* d_probs, float* d_logits, void* stream);
+/*
+ * ABI 2.9: the launches a forward of B reads at length (ragged = 0) or row pitch (ragged = 1) L makes, in order, in the program's
+ * current mode.  Read-only: the forward takes every decision from the same planner.  The per-read length table of a ragged batch
+ * and the classifier head are not listed.  Writes the first min(*n, cap) entries to out (out may be NULL when cap is 0) and the
+ * number of launches to *n.  Refuses (RS_ERR_ARG / RS_ERR_LENGTH, with the forward's error text) what the forward refuses:
+ * a null model or n, B < 1, an L too short for the program, a ragged call on a program that is not ragged_ok or whose fused
+ * launches outgrow the buffer windows.
+ */
+enum {
+    RS_SEQ_STEM_POOL = 1,     /* seq_stem_pool_kernel<nt> (x3: seq_stem_pool_x3_kernel): stem conv + ReLU + MaxPool(2, 2, 1) */
+    RS_SEQ_BASIC_BLOCK = 2,   /* seq_basic_block_kernel<nt, mtw, waves> (x3: seq_basic_block_x3_kernel) */
+    RS_SEQ_BOTTLENECK = 3,    /* seq_bottleneck_block_kernel<ntm, nt> (x3: seq_bottleneck_block_x3_kernel) */
+    RS_SEQ_CONV_MFMA_LDS = 4, /* seq_conv_mfma_lds_kernel<nt>: one conv, packed weights in LDS */
+    RS_SEQ_CONV_MFMA = 5,     /* seq_conv_mfma_kernel<nt>: one conv, weights from global memory, ceil(c_out / 16 nt) column groups */
+    RS_SEQ_CONV_SCALAR = 6,   /* seq_conv_kernel (RS_SEQ_SCALAR) */
+    RS_SEQ_MAXPOOL = 7,       /* seq_maxpool_kernel */
+};
+typedef struct rs_seq_launch {
+    int32_t op, n_ops;        /* first op index of the program, ops the launch covers */
+    int32_t family;           /* RS_SEQ_* above */
+    int32_t nt, ntm, mtw, waves;   /* template arguments (0 where the kernel has none; ntm: bottleneck mid tiles) */
+    int32_t np;               /* weight column pitch (the output columns' for a bottleneck); 0 for the scalar conv and the pool */
+    int32_t cp;               /* row pitch of the intermediate tile in LDS (floats, or bf16 halfwords when x3); 0 without one */
+    int32_t x3;               /* 1: split precision on the bf16 MFMA */
+} rs_seq_launch;
+RS_API int rs_seqnet_launch_plan(const rs_seqnet* m, int B, int L, int ragged, rs_seq_launch* out, int cap, int* n);
 
 /*
  * ABI 2.6: TCN and bottleneck TCN (riser/nets/tcn.py:62-91, riser/nets/tcn_bot.py:63-92; chosen by riser/train.py:175-182

@@ -25,6 +25,7 @@ SYMBOLS = (
     "rs_classify_ensemble", "rs_ensemble_workspace_bytes", "rs_autotune", "rs_decide", "rs_polya_end", "rs_copy_segments", "rs_model_layer_info", "rs_profile_enable", "rs_profile_read",
     "rs_debug_capture_layer", "rs_polya_end_resume", "rs_model_saturated",
     "rs_seqnet_create", "rs_seqnet_destroy", "rs_seqnet_workspace_bytes", "rs_seqnet_forward", "rs_seqnet_set_mode", "rs_seqnet_ragged_ok", "rs_seqnet_forward_ragged", "rs_seqnet_max_batch",
+    "rs_seqnet_launch_plan",
     "rs_tcn_create", "rs_tcn_destroy", "rs_tcn_receptive_field", "rs_tcn_workspace_bytes", "rs_tcn_max_batch", "rs_tcn_forward_ragged", "rs_tcn_set_mode",
     "rs_tcn_tile_plan",
     "rs_crnn_create", "rs_crnn_destroy", "rs_crnn_min_length", "rs_crnn_steps", "rs_crnn_workspace_bytes", "rs_crnn_max_batch",
@@ -35,6 +36,16 @@ SYMBOLS = (
 class SeqOp(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kind", "src", "dst", "add", "c_in", "c_out", "k", "stride", "pad", "relu")] + \
                [("w", C.c_void_p), ("b", C.c_void_p)]
+
+
+class SeqLaunch(C.Structure):
+    """rs_seq_launch: one launch of a conv program's forward (rs_seqnet_launch_plan)"""
+    _fields_ = [(n, C.c_int32) for n in ("op", "n_ops", "family", "nt", "ntm", "mtw", "waves", "np", "cp", "x3")]
+
+
+# rs_seq_launch.family
+RS_SEQ_FAMILIES = {1: "stem_pool", 2: "basic_block", 3: "bottleneck", 4: "conv_mfma_lds", 5: "conv_mfma", 6: "conv_scalar",
+                   7: "maxpool"}
 
 
 class LayerInfo(C.Structure):
@@ -120,6 +131,8 @@ def lib():
     L.rs_seqnet_max_batch.argtypes = [vp, i32]
     L.rs_seqnet_forward_ragged.restype = i32
     L.rs_seqnet_forward_ragged.argtypes = [vp, vp, vp, i32, i32, vp, sz, vp, vp, vp]
+    L.rs_seqnet_launch_plan.restype = i32
+    L.rs_seqnet_launch_plan.argtypes = [vp, i32, i32, i32, C.POINTER(SeqLaunch), i32, C.POINTER(i32)]
     L.rs_tcn_create.restype = i32
     L.rs_tcn_create.argtypes = [vp, i32, vp, vp, i32, i32, C.POINTER(vp)]
     L.rs_tcn_destroy.restype = i32

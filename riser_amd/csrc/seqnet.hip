@@ -1988,6 +1988,137 @@ size_t buffer_bytes(const rs_seqnet* m, int B, int L) {
     return ((size_t)B * elems * sizeof(float) + 255) / 256 * 256;
 }
 
+// One launch of a forward: what seqnet_forward_impl runs and rs_seqnet_launch_plan reports (rs_seq_launch), plus the dynamic LDS
+struct Launch {
+    int op = 0, n_ops = 1, family = 0;
+    int nt = 0, ntm = 0, mtw = 0, waves = 0, np = 0, cp = 0, x3 = 0;
+    size_t lds = 0;
+};
+
+// tile of a basic block = (row tiles per wave, waves): rows R = 16 * mtw * waves of the intermediate, R - 2 outputs.  More rows
+// per wave = fewer halo rows, weight-fragment reads and set-up instructions per MFMA; candidates must fit the LDS next to the
+// weights, should leave room for a second workgroup on the CU, and must not waste more than ~6 % of their rows behind the end of
+// the read; a block so wide that one workgroup owns the CU's LDS runs eight waves (two per SIMD: with one, every LDS / global
+// round trip idles the matrix pipe).  w_bytes: the weights in LDS, row_bytes: one tile row (both planes in split precision).
+// (256-row tiles - four row tiles per wave - were measured on the 20-channel stage: 168 against 165 us)
+void block_tile(size_t w_bytes, size_t row_bytes, int t_out, Launch& l) {
+    const size_t lds_cap = 160 * 1024;
+    auto lds_of = [&](int rows) { return w_bytes + (size_t)(rows + 4) * row_bytes; };
+    auto waste = [&](int rows) {
+        const int to = rows - 2, n = (t_out + to - 1) / to;
+        return (double)(n * to - t_out) / (double)(n * to);
+    };
+    l.mtw = 1;
+    l.waves = 4;
+    if (lds_cap / lds_of(64) < 2) {
+        if (lds_of(128) <= lds_cap) l.waves = 8;
+    } else {
+        if (lds_cap / lds_of(128) >= 2 && waste(128) < 0.06) l.mtw = 2;
+    }
+    l.lds = lds_of(16 * l.mtw * l.waves);
+}
+
+// Every launch decision of a forward of B reads at length (or, ragged, row pitch) L in the program's current mode: which ops fuse
+// into one launch (the fused forms need their buffers inside the 32-bit-offset windows), split precision or fp32, the tile of a
+// basic block, the unfused kernel of every other op.  seqnet_forward_impl launches exactly this list and rs_seqnet_launch_plan
+// reports it.  On a refusal: the forward's error text and code.  shp: per-op shapes, last / last_op: the head's input.
+int plan_launches(const rs_seqnet* m, int B, int L, bool ragged, std::vector<Launch>& out, std::vector<OpShape>& shp, int& last,
+                  int& last_op) {
+    out.clear();
+    if (ragged && !rs_seqnet_ragged_ok(m)) {
+        set_error("rs_seqnet_forward_ragged: this program has ops outside its fused launches (stem, residual blocks): group the "
+                  "reads by length and call rs_seqnet_forward");
+        return RS_ERR_ARG;
+    }
+    std::vector<int> T, C;                                         // buffer ids are reused: shapes are per op
+    if (!propagate(m, L, T, C, nullptr, &shp)) {
+        set_error("rs_seqnet_forward: input of %d samples is too short for this network", L);
+        return RS_ERR_LENGTH;
+    }
+    last = 0;
+    last_op = -1;
+    for (size_t k = 0; k < m->ops.size(); ++k) {
+        const OpDev& o = m->ops[k];
+        const OpShape& sh = shp[k];
+        Launch l;
+        l.op = (int)k;
+        if (o.fuse == 1 && (int64_t)B * 2 * shp[k + 1].t_out < m->window && (int64_t)B * sh.t_in * 4 < m->window) {
+            // stem conv + ReLU + MaxPool(2, 2, pad 1) in one launch: GEMM rows = 2 * pooled rows
+            l.family = RS_SEQ_STEM_POOL;
+            l.nt = o.nt;
+            l.np = 16 * o.nt;
+            if (m->mode == 1 && o.d_x_w1) {                        // the stem in split precision on the bf16 MFMA
+                l.x3 = 1;
+                l.lds = (size_t)o.x_s1 * 4 * o.nt * 16 * 8 * 2 * 2 + (size_t)4 * 16 * o.c_out * 4;
+            } else {
+                l.lds = (size_t)((o.k * o.c_in + 15) & ~15) * o.nt * 16 * 4;
+            }
+        } else if (o.fuse == 2 && (int64_t)B * shp[k + o.fuse_skip].t_in * o.f_cout * 4 < m->window &&
+                   (int64_t)B * shp[k + o.fuse_skip - 1].t_in * o.f_cin * 4 < m->window) {
+            // residual basic block in one launch (shapes of its first 3x3 conv: ops[k + fuse_skip - 1]); in split precision the
+            // same tiling rules over its own LDS footprint
+            const int t_out = shp[k + o.fuse_skip - 1].t_out;
+            l.family = RS_SEQ_BASIC_BLOCK;
+            l.nt = o.f_nt;
+            if (m->mode == 1 && o.d_x_w1) {
+                l.x3 = 1;
+                l.np = o.x_np;
+                l.cp = o.x_cp;
+                block_tile(o.x_wbytes, (size_t)o.x_cp * 4, t_out, l);
+            } else {
+                l.np = o.f_nps;
+                l.cp = o.f_cp;
+                block_tile(o.f_wfloats * 4, (size_t)o.f_cp * 4, t_out, l);
+            }
+        } else if (o.fuse == 3 && (int64_t)B * shp[k + o.fuse_skip - 2].t_in * o.f_cin * 4 < m->window &&
+                   (int64_t)B * shp[k + o.fuse_skip - 1].t_out * o.f_cout * 4 < m->window) {
+            // residual bottleneck block in one launch; shapes: conv 1 = ops[k + skip - 2], conv 2 (the strided one) = [k + skip - 1]
+            l.family = RS_SEQ_BOTTLENECK;
+            l.ntm = o.f_ntm;
+            l.nt = o.f_nt;
+            l.np = o.f_nps;
+            if (m->mode == 1 && m->bneck_x3 && o.d_x_w1) {
+                l.x3 = 1;
+                l.cp = o.x_cp;
+                l.lds = o.x_wbytes + (size_t)2 * (128 + 4) * o.x_cp * 4;
+            } else {
+                l.cp = o.f_cp;
+                l.lds = (o.f_wfloats + (size_t)2 * (128 + 4) * o.f_cp) * 4;
+            }
+        } else if (ragged) {
+            // a ragged batch runs in fused launches only (they mask by every read's own rows; the unfused kernels below treat
+            // every read as `ld` samples long): a fused launch that does not fit its 2 GiB buffer windows is an error, not a
+            // silent fall-through to wrong probabilities (ADVICE round 5)
+            set_error("rs_seqnet_forward_ragged: op %zu of the program cannot run as a fused launch on %d reads of pitch %d (a buffer "
+                      "beyond the 2 GiB window): split the batch", k, B, L);
+            return RS_ERR_ARG;
+        } else if (o.kind == 0 && m->scalar_conv) {
+            l.family = RS_SEQ_CONV_SCALAR;
+        } else if (o.kind == 0 && o.d_wq && (int64_t)B * sh.t_in * o.c_in * 4 < m->window) {
+            l.family = RS_SEQ_CONV_MFMA_LDS;
+            l.nt = o.nt;
+            l.np = 16 * o.nt;
+            l.lds = (size_t)((o.k * o.c_in + 15) & ~15) * o.nt * 16 * 4;
+        } else if (o.kind == 0) {
+            l.family = RS_SEQ_CONV_MFMA;
+            l.nt = o.c_out <= 16 ? 1 : o.c_out <= 32 ? 2 : 4;
+            l.np = (o.c_out + 3) / 4 * 4;
+        } else {
+            l.family = RS_SEQ_MAXPOOL;
+        }
+        l.n_ops = l.family <= RS_SEQ_BOTTLENECK ? 1 + o.fuse_skip : 1;
+        last = l.family <= RS_SEQ_BOTTLENECK ? o.f_dst : o.dst;
+        last_op = (int)k + l.n_ops - 1;
+        k += l.n_ops - 1;
+        out.push_back(l);
+    }
+    if (C[last] != m->c_last) {
+        set_error("rs_seqnet_forward: last buffer has %d channels, classifier expects %d", C[last], m->c_last);
+        return RS_ERR_ARG;
+    }
+    return RS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2180,23 +2311,34 @@ int rs_seqnet_ragged_ok(const rs_seqnet* m) {
     return m->ops.size() <= 63 ? 1 : 0;
 }
 
+int rs_seqnet_launch_plan(const rs_seqnet* m, int B, int L, int ragged, rs_seq_launch* out, int cap, int* n) {
+    if (!m || !n || B < 1 || L < 1 || cap < 0 || (cap > 0 && !out)) {
+        set_error("rs_seqnet_launch_plan: bad argument");
+        return RS_ERR_ARG;
+    }
+    std::vector<Launch> plan;
+    std::vector<OpShape> shp;
+    int last = 0, last_op = -1;
+    const int rc = plan_launches(m, B, L, ragged != 0, plan, shp, last, last_op);
+    if (rc != RS_OK) return rc;
+    for (size_t i = 0; i < plan.size() && (int)i < cap; ++i) {
+        const Launch& l = plan[i];
+        out[i] = rs_seq_launch{l.op, l.n_ops, l.family, l.nt, l.ntm, l.mtw, l.waves, l.np, l.cp, l.x3};
+    }
+    *n = (int)plan.size();
+    return RS_OK;
+}
+
 static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_len, int B, int L, void* d_ws, size_t ws_bytes,
                                float* d_probs, float* d_logits, void* stream) {
     if (!m || !d_x || !d_ws || !d_probs || B < 1 || L < 1) {
         set_error("rs_seqnet_forward: bad argument");
         return RS_ERR_ARG;
     }
-    if (d_len && !rs_seqnet_ragged_ok(m)) {
-        set_error("rs_seqnet_forward_ragged: this program has ops outside its fused launches (stem, residual blocks): group the "
-                  "reads by length and call rs_seqnet_forward");
-        return RS_ERR_ARG;
-    }
-    std::vector<int> T, C;
-    std::vector<OpShape> shp;                                      // buffer ids are reused: shapes are per op
-    if (!propagate(m, L, T, C, nullptr, &shp)) {
-        set_error("rs_seqnet_forward: input of %d samples is too short for this network", L);
-        return RS_ERR_LENGTH;
-    }
+    std::vector<Launch> plan;
+    std::vector<OpShape> shp;
+    int last = 0, last_op = -1;
+    if (const int rc = plan_launches(m, B, L, d_len != nullptr, plan, shp, last, last_op); rc != RS_OK) return rc;
     const size_t per = buffer_bytes(m, B, L);
     if (ws_bytes < rs_seqnet_workspace_bytes(m, B, L)) {
         set_error("rs_seqnet_forward: workspace too small");
@@ -2231,53 +2373,41 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
         RS_HIP(hipGetLastError());
     }
     auto rows_after = [&](int op) -> const int32_t* { return table ? table + (size_t)(op + 1) * B : nullptr; };   // op = -1: the input
-    int last = 0, last_op = -1;
-    for (size_t k = 0; k < m->ops.size(); ++k) {
+    const size_t lds_cap = 160 * 1024;
+    for (const Launch& l : plan) {
+        const size_t k = (size_t)l.op;
         const OpDev& o = m->ops[k];
         const OpShape& sh = shp[k];
-        if (o.fuse == 1 && (int64_t)B * 2 * shp[k + 1].t_out < m->window && (int64_t)B * sh.t_in * 4 < m->window) {
-            // stem conv + ReLU + MaxPool(2, 2, pad 1) in one launch: GEMM rows = 2 * pooled rows
+        if (l.family == RS_SEQ_STEM_POOL) {
             const OpShape& ps = shp[k + 1];
             const int rows = B * 2 * ps.t_out;
             const int n_tiles = (rows + 127) / 128;
-            if (m->mode == 1 && o.d_x_w1) {                        // the stem in split precision on the bf16 MFMA
-                const size_t lds = (size_t)o.x_s1 * 4 * o.nt * 16 * 8 * 2 * 2 + (size_t)4 * 16 * o.c_out * 4;
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, lds_cap / std::max<size_t>(l.lds, 1)));
+            const int grid = std::min(n_tiles, m->num_cu * per_cu);
+            if (l.x3) {
                 auto fx = o.nt == 1 ? seq_stem_pool_x3_kernel<1> : o.nt == 2 ? seq_stem_pool_x3_kernel<2> : o.nt == 3 ? seq_stem_pool_x3_kernel<3>
                         : o.nt == 4 ? seq_stem_pool_x3_kernel<4> : seq_stem_pool_x3_kernel<5>;
                 RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fx), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
-                const int grid = std::min(n_tiles, m->num_cu * per_cu);
-                hipLaunchKernelGGL(fx, dim3(grid), dim3(256), lds, st, buf(o.f_src), (unsigned)((int64_t)B * sh.t_in * 4), o.d_x_w1, o.d_b,
+                hipLaunchKernelGGL(fx, dim3(grid), dim3(256), l.lds, st, buf(o.f_src), (unsigned)((int64_t)B * sh.t_in * 4), o.d_x_w1, o.d_b,
                                    buf(o.f_dst), B, sh.t_in, sh.t_out, ps.t_out, o.c_out, o.k * o.c_in, o.x_s1, o.stride, o.pad, n_tiles,
                                    rows_after(prod[k]), rows_after((int)k));
-                RS_HIP(hipGetLastError());
-                last = o.f_dst;
-                last_op = (int)(k + o.fuse_skip);
-                k += o.fuse_skip;
-                continue;
+            } else {
+                auto fn = o.nt == 1 ? seq_stem_pool_kernel<1> : o.nt == 2 ? seq_stem_pool_kernel<2> : o.nt == 3 ? seq_stem_pool_kernel<3>
+                        : o.nt == 4 ? seq_stem_pool_kernel<4> : seq_stem_pool_kernel<5>;
+                RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+                hipLaunchKernelGGL(fn, dim3(grid), dim3(256), l.lds, st, buf(o.f_src), (unsigned)((int64_t)B * sh.t_in * 4), o.d_wq, o.d_b,
+                                   buf(o.f_dst), B, sh.t_in, sh.t_out, ps.t_out, o.c_out, o.k * o.c_in, o.stride, o.pad, n_tiles,
+                                   rows_after(prod[k]), rows_after((int)k));
             }
-            const int K = o.k * o.c_in, K16 = (K + 15) & ~15;
-            const size_t lds = (size_t)K16 * o.nt * 16 * 4;
-            auto fn = o.nt == 1 ? seq_stem_pool_kernel<1> : o.nt == 2 ? seq_stem_pool_kernel<2> : o.nt == 3 ? seq_stem_pool_kernel<3>
-                    : o.nt == 4 ? seq_stem_pool_kernel<4> : seq_stem_pool_kernel<5>;
-            RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
-            const int grid = std::min(n_tiles, m->num_cu * per_cu);
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, st, buf(o.f_src), (unsigned)((int64_t)B * sh.t_in * 4), o.d_wq, o.d_b,
-                               buf(o.f_dst), B, sh.t_in, sh.t_out, ps.t_out, o.c_out, K, o.stride, o.pad, n_tiles, rows_after(prod[k]),
-                               rows_after((int)k));
-            RS_HIP(hipGetLastError());
-            last = o.f_dst;
-            last_op = (int)(k + o.fuse_skip);
-            k += o.fuse_skip;
-            continue;
-        }
-        if (o.fuse == 2 && (int64_t)B * shp[k + o.fuse_skip].t_in * o.f_cout * 4 < m->window) {
-            // residual basic block in one launch (shapes of its first 3x3 conv: ops[k + fuse_skip - 1])
+        } else if (l.family == RS_SEQ_BASIC_BLOCK) {
             const OpShape& s1 = shp[k + o.fuse_skip - 1];
             const int64_t xb = (int64_t)B * s1.t_in * o.f_cin * 4;
-            if (xb < m->window && m->mode == 1 && o.d_x_w1) {
-                // the block in split precision on the bf16 MFMA: same tiling rules, its own LDS footprint
+            const int TO = 16 * l.mtw * l.waves - 2;
+            const int tiles_per_read = (s1.t_out + TO - 1) / TO;
+            const int col = l.waves == 8 ? 2 : l.mtw - 1;     // [4 waves x 1 | 4 waves x 2 | 8 waves x 1 row tiles per wave]
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, lds_cap / l.lds));
+            const int grid = std::min(B * tiles_per_read, m->num_cu * per_cu);
+            if (l.x3) {
                 BlockX3Args a;
                 a.x = buf(o.f_src);
                 a.x_bytes = (unsigned)xb;
@@ -2301,22 +2431,8 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                 a.Ssc = o.x_ssc;
                 a.tin = rows_after(prod[k + o.fuse_skip - 1]);
                 a.tout = rows_after((int)(k + o.fuse_skip - 1));
-                const size_t lds_cap = 160 * 1024;
-                auto lds_of = [&](int rows) { return o.x_wbytes + (size_t)(rows + 4) * o.x_cp * 4; };
-                auto waste = [&](int rows) {
-                    const int to = rows - 2, n = (s1.t_out + to - 1) / to;
-                    return (double)(n * to - s1.t_out) / (double)(n * to);
-                };
-                int mtw = 1, waves = 4;
-                if (lds_cap / lds_of(64) < 2) {
-                    if (lds_of(128) <= lds_cap) waves = 8;
-                } else {
-                    if (lds_cap / lds_of(128) >= 2 && waste(128) < 0.06) mtw = 2;
-                }
-                const size_t f_lds = lds_of(16 * mtw * waves);
-                const int TO = 16 * mtw * waves - 2;
-                a.tiles_per_read = (s1.t_out + TO - 1) / TO;
-                a.n_tiles = B * a.tiles_per_read;
+                a.tiles_per_read = tiles_per_read;
+                a.n_tiles = B * tiles_per_read;
                 using Fn = void (*)(const BlockX3Args);
                 static const Fn table[5][3] = {
                     {seq_basic_block_x3_kernel<1, 1, 4>, seq_basic_block_x3_kernel<1, 2, 4>, seq_basic_block_x3_kernel<1, 1, 8>},
@@ -2324,18 +2440,10 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                     {seq_basic_block_x3_kernel<3, 1, 4>, seq_basic_block_x3_kernel<3, 2, 4>, seq_basic_block_x3_kernel<3, 1, 8>},
                     {seq_basic_block_x3_kernel<4, 1, 4>, seq_basic_block_x3_kernel<4, 2, 4>, seq_basic_block_x3_kernel<4, 1, 8>},
                     {seq_basic_block_x3_kernel<5, 1, 4>, seq_basic_block_x3_kernel<5, 2, 4>, seq_basic_block_x3_kernel<5, 1, 8>}};
-                Fn fn = table[o.f_nt - 1][waves == 8 ? 2 : mtw - 1];
+                Fn fn = table[o.f_nt - 1][col];
                 RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, lds_cap / f_lds));
-                const int grid = std::min(a.n_tiles, m->num_cu * per_cu);
-                hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * waves), f_lds, st, a);
-                RS_HIP(hipGetLastError());
-                last = o.f_dst;
-                last_op = (int)(k + o.fuse_skip);
-                k += o.fuse_skip;
-                continue;
-            }
-            if (xb < m->window) {
+                hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * l.waves), l.lds, st, a);
+            } else {
                 BlockArgs a;
                 a.x = buf(o.f_src);
                 a.x_bytes = (unsigned)xb;
@@ -2357,53 +2465,28 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                 a.Ksc = o.f_ksc;
                 a.tin = rows_after(prod[k + o.fuse_skip - 1]);
                 a.tout = rows_after((int)(k + o.fuse_skip - 1));
-                // tile = (row tiles per wave, waves): rows R = 16 * mtw * waves of the intermediate, R - 2 outputs.  More rows
-                // per wave = fewer halo rows, weight-fragment reads and set-up instructions per MFMA; candidates must fit the
-                // LDS next to the weights, should leave room for a second workgroup on the CU, and must not waste more than
-                // ~6 % of their rows behind the end of the read; a block so wide that one workgroup owns the CU's LDS runs
-                // eight waves (two per SIMD: with one, every LDS / global round trip idles the matrix pipe)
-                const size_t lds_cap = 160 * 1024;
-                auto lds_of = [&](int rows) { return (o.f_wfloats + (size_t)(rows + 4) * o.f_cp) * 4; };
-                auto waste = [&](int rows) {
-                    const int to = rows - 2, n = (s1.t_out + to - 1) / to;
-                    return (double)(n * to - s1.t_out) / (double)(n * to);
-                };
-                int mtw = 1, waves = 4;
-                if (lds_cap / lds_of(64) < 2) {
-                    if (lds_of(128) <= lds_cap) waves = 8;
-                } else {
-                    if (lds_cap / lds_of(128) >= 2 && waste(128) < 0.06) mtw = 2;
-                }
-                const size_t f_lds = lds_of(16 * mtw * waves);
-                const int TO = 16 * mtw * waves - 2;
-                a.tiles_per_read = (s1.t_out + TO - 1) / TO;
-                a.n_tiles = B * a.tiles_per_read;
+                a.tiles_per_read = tiles_per_read;
+                a.n_tiles = B * tiles_per_read;
                 using Fn = void (*)(const BlockArgs);
-                static const Fn table[5][3] = {   // [NT - 1][4 waves x 1 | 4 waves x 2 | 8 waves x 1 row tiles per wave]
+                static const Fn table[5][3] = {
                     {seq_basic_block_kernel<1, 1, 4>, seq_basic_block_kernel<1, 2, 4>, seq_basic_block_kernel<1, 1, 8>},
                     {seq_basic_block_kernel<2, 1, 4>, seq_basic_block_kernel<2, 2, 4>, seq_basic_block_kernel<2, 1, 8>},
                     {seq_basic_block_kernel<3, 1, 4>, seq_basic_block_kernel<3, 2, 4>, seq_basic_block_kernel<3, 1, 8>},
                     {seq_basic_block_kernel<4, 1, 4>, seq_basic_block_kernel<4, 2, 4>, seq_basic_block_kernel<4, 1, 8>},
                     {seq_basic_block_kernel<5, 1, 4>, seq_basic_block_kernel<5, 2, 4>, seq_basic_block_kernel<5, 1, 8>}};
-                // (256-row tiles - four row tiles per wave - were measured on the 20-channel stage: 168 against 165 us)
-                Fn fn = table[o.f_nt - 1][waves == 8 ? 2 : mtw - 1];
+                Fn fn = table[o.f_nt - 1][col];
                 RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, lds_cap / f_lds));
-                const int grid = std::min(a.n_tiles, m->num_cu * per_cu);
-                hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * waves), f_lds, st, a);
-                RS_HIP(hipGetLastError());
-                last = o.f_dst;
-                last_op = (int)(k + o.fuse_skip);
-                k += o.fuse_skip;
-                continue;
+                hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * l.waves), l.lds, st, a);
             }
-        }
-        if (o.fuse == 3) {
-            // residual bottleneck block in one launch; shapes: conv 1 = ops[k + skip - 2], conv 2 (the strided one) = [k + skip - 1]
+        } else if (l.family == RS_SEQ_BOTTLENECK) {
             const OpShape& s1 = shp[k + o.fuse_skip - 2];
             const OpShape& s2 = shp[k + o.fuse_skip - 1];
             const int64_t xb = (int64_t)B * s1.t_in * o.f_cin * 4;
-            if (xb < m->window && (int64_t)B * s2.t_out * o.f_cout * 4 < m->window && m->mode == 1 && m->bneck_x3 && o.d_x_w1) {
+            const int R2 = (128 - 3) / o.f_stride + 1;
+            const int tiles_per_read = (s2.t_out + R2 - 1) / R2;
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, lds_cap / l.lds));
+            const int grid = std::min(B * tiles_per_read, m->num_cu * per_cu);
+            if (l.x3) {
                 BneckX3Args a;
                 a.x = buf(o.f_src);
                 a.x_bytes = (unsigned)xb;
@@ -2424,9 +2507,9 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                 a.S1 = o.x_s1; a.S2 = o.x_s2a; a.S3 = o.x_s3; a.Ssc = o.x_ssc;
                 a.tin = rows_after(prod[k + o.fuse_skip - 2]);
                 a.tout = rows_after((int)(k + o.fuse_skip - 1));
-                a.R2 = (128 - 3) / o.f_stride + 1;
-                a.tiles_per_read = (s2.t_out + a.R2 - 1) / a.R2;
-                a.n_tiles = B * a.tiles_per_read;
+                a.R2 = R2;
+                a.tiles_per_read = tiles_per_read;
+                a.n_tiles = B * tiles_per_read;
                 using FnX = void (*)(const BneckX3Args);
                 static const FnX tablex[2][5] = {
                     {seq_bottleneck_block_x3_kernel<1, 1>, seq_bottleneck_block_x3_kernel<1, 2>, seq_bottleneck_block_x3_kernel<1, 3>,
@@ -2434,18 +2517,9 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                     {seq_bottleneck_block_x3_kernel<2, 1>, seq_bottleneck_block_x3_kernel<2, 2>, seq_bottleneck_block_x3_kernel<2, 3>,
                      seq_bottleneck_block_x3_kernel<2, 4>, seq_bottleneck_block_x3_kernel<2, 5>}};
                 FnX fx = tablex[o.f_ntm - 1][o.f_nt - 1];
-                const size_t f_lds = o.x_wbytes + (size_t)2 * (128 + 4) * o.x_cp * 4;
                 RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fx), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)(160 * 1024) / f_lds));
-                const int grid = std::min(a.n_tiles, m->num_cu * per_cu);
-                hipLaunchKernelGGL(fx, dim3(grid), dim3(256), f_lds, st, a);
-                RS_HIP(hipGetLastError());
-                last = o.f_dst;
-                last_op = (int)(k + o.fuse_skip);
-                k += o.fuse_skip;
-                continue;
-            }
-            if (xb < m->window && (int64_t)B * s2.t_out * o.f_cout * 4 < m->window) {
+                hipLaunchKernelGGL(fx, dim3(grid), dim3(256), l.lds, st, a);
+            } else {
                 BneckArgs a;
                 a.x = buf(o.f_src);
                 a.x_bytes = (unsigned)xb;
@@ -2464,9 +2538,9 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                 a.Ksc = o.f_ksc;
                 a.tin = rows_after(prod[k + o.fuse_skip - 2]);
                 a.tout = rows_after((int)(k + o.fuse_skip - 1));
-                a.R2 = (128 - 3) / o.f_stride + 1;
-                a.tiles_per_read = (s2.t_out + a.R2 - 1) / a.R2;
-                a.n_tiles = B * a.tiles_per_read;
+                a.R2 = R2;
+                a.tiles_per_read = tiles_per_read;
+                a.n_tiles = B * tiles_per_read;
                 using Fn = void (*)(const BneckArgs);
                 static const Fn table[2][5] = {
                     {seq_bottleneck_block_kernel<1, 1>, seq_bottleneck_block_kernel<1, 2>, seq_bottleneck_block_kernel<1, 3>,
@@ -2474,54 +2548,33 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                     {seq_bottleneck_block_kernel<2, 1>, seq_bottleneck_block_kernel<2, 2>, seq_bottleneck_block_kernel<2, 3>,
                      seq_bottleneck_block_kernel<2, 4>, seq_bottleneck_block_kernel<2, 5>}};
                 Fn fn = table[o.f_ntm - 1][o.f_nt - 1];
-                const size_t f_lds = (o.f_wfloats + (size_t)2 * (128 + 4) * o.f_cp) * 4;
                 RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (size_t)(160 * 1024) / f_lds));
-                const int grid = std::min(a.n_tiles, m->num_cu * per_cu);
-                hipLaunchKernelGGL(fn, dim3(grid), dim3(256), f_lds, st, a);
-                RS_HIP(hipGetLastError());
-                last = o.f_dst;
-                last_op = (int)(k + o.fuse_skip);
-                k += o.fuse_skip;
-                continue;
+                hipLaunchKernelGGL(fn, dim3(grid), dim3(256), l.lds, st, a);
             }
-        }
-        if (d_len) {
-            // a ragged batch runs in fused launches only (they mask by every read's own rows; the unfused kernels below treat
-            // every read as `ld` samples long): a fused launch that does not fit its 2 GiB buffer windows is an error, not a
-            // silent fall-through to wrong probabilities (ADVICE round 5)
-            set_error("rs_seqnet_forward_ragged: op %zu of the program cannot run as a fused launch on %d reads of pitch %d (a buffer "
-                      "beyond the 2 GiB window): split the batch", k, B, L);
-            return RS_ERR_ARG;
-        }
-        if (o.kind == 0 && m->scalar_conv) {
+        } else if (l.family == RS_SEQ_CONV_SCALAR) {
             const int cq = (o.c_out + 3) / 4;
             const int64_t total = (int64_t)B * sh.t_out * cq;
             hipLaunchKernelGGL(seq_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, buf(o.src),
                                o.d_w, o.d_b, o.add >= 0 ? buf(o.add) : nullptr, buf(o.dst), B, sh.t_in, sh.t_out,
                                o.c_in, o.c_out, cq, o.k, o.stride, o.pad, o.relu);
-        } else if (o.kind == 0 && o.d_wq && (int64_t)B * sh.t_in * o.c_in * 4 < m->window) {
+        } else if (l.family == RS_SEQ_CONV_MFMA_LDS) {
             const int64_t rows = (int64_t)B * sh.t_out;
             const int n_tiles = (int)((rows + 127) / 128);
-            const int K = o.k * o.c_in, K16 = (K + 15) & ~15;
-            const size_t lds = (size_t)K16 * o.nt * 16 * 4;
             auto fn = o.nt == 1 ? seq_conv_mfma_lds_kernel<1> : o.nt == 2 ? seq_conv_mfma_lds_kernel<2>
                     : o.nt == 3 ? seq_conv_mfma_lds_kernel<3> : o.nt == 4 ? seq_conv_mfma_lds_kernel<4> : seq_conv_mfma_lds_kernel<5>;
             RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
             // small workgroups (256 threads, <= 96 KB LDS, few registers): as many per CU as the weights in LDS allow
-            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / std::max<size_t>(lds, 1)));
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, lds_cap / std::max<size_t>(l.lds, 1)));
             const int grid = std::min(n_tiles, m->num_cu * per_cu);
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, st, buf(o.src), (unsigned)((int64_t)B * sh.t_in * o.c_in * 4),
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(256), l.lds, st, buf(o.src), (unsigned)((int64_t)B * sh.t_in * o.c_in * 4),
                                o.d_wq, o.d_b, o.add >= 0 ? buf(o.add) : nullptr, buf(o.dst), B, sh.t_in, sh.t_out, o.c_in,
-                               o.c_out, K, o.stride, o.pad, o.relu, n_tiles);
-        } else if (o.kind == 0) {
-            const int cq = (o.c_out + 3) / 4;
+                               o.c_out, o.k * o.c_in, o.stride, o.pad, o.relu, n_tiles);
+        } else if (l.family == RS_SEQ_CONV_MFMA) {
             const int64_t rows = (int64_t)B * sh.t_out;
-            const int nt = o.c_out <= 16 ? 1 : o.c_out <= 32 ? 2 : 4;
-            const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((o.c_out + 16 * nt - 1) / (16 * nt)));
-            auto fn = nt == 1 ? seq_conv_mfma_kernel<1> : nt == 2 ? seq_conv_mfma_kernel<2> : seq_conv_mfma_kernel<4>;
+            const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)((o.c_out + 16 * l.nt - 1) / (16 * l.nt)));
+            auto fn = l.nt == 1 ? seq_conv_mfma_kernel<1> : l.nt == 2 ? seq_conv_mfma_kernel<2> : seq_conv_mfma_kernel<4>;
             hipLaunchKernelGGL(fn, grid, dim3(256), 0, st, buf(o.src), o.d_w, o.d_b, o.add >= 0 ? buf(o.add) : nullptr,
-                               buf(o.dst), B, sh.t_in, sh.t_out, o.c_in, o.c_out, cq * 4, o.k * o.c_in, o.stride, o.pad,
+                               buf(o.dst), B, sh.t_in, sh.t_out, o.c_in, o.c_out, l.np, o.k * o.c_in, o.stride, o.pad,
                                o.relu);
         } else {
             const int64_t total = (int64_t)B * sh.t_out * sh.c;
@@ -2529,14 +2582,8 @@ static int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_
                                buf(o.src), buf(o.dst), B, sh.t_in, sh.t_out, sh.c, o.pad);
         }
         RS_HIP(hipGetLastError());
-        last = o.dst;
-        last_op = (int)k;
     }
-    if (C[last] != m->c_last) {
-        set_error("rs_seqnet_forward: last buffer has %d channels, classifier expects %d", C[last], m->c_last);
-        return RS_ERR_ARG;
-    }
-    hipLaunchKernelGGL(seq_head_kernel, dim3(B), dim3(256), 0, st, buf(last), T[last], m->c_last, m->d_fcw, m->d_fcb,
+    hipLaunchKernelGGL(seq_head_kernel, dim3(B), dim3(256), 0, st, buf(last), shp[last_op].t_out, m->c_last, m->d_fcw, m->d_fcb,
                        d_probs, d_logits, rows_after(last_op));
     RS_HIP(hipGetLastError());
     return RS_OK;

@@ -203,6 +203,20 @@ class SeqNet:
         2 GiB buffer window (rs_seqnet_max_batch); bigger batches are split by the callers below and in riser_amd.Model"""
         return max(1, int(nv.lib().rs_seqnet_max_batch(self._h, int(L))))
 
+    def launch_plan(self, B: int, L: int, ragged: bool = False):
+        """the launches a forward of B reads at length (ragged: row pitch) L makes in the current mode (rs_seqnet_launch_plan):
+        dicts of rs_seq_launch's fields, the family by name"""
+        lib, n = nv.lib(), C.c_int32(0)
+        nv.check(lib.rs_seqnet_launch_plan(self._h, int(B), int(L), int(ragged), None, 0, C.byref(n)), "rs_seqnet_launch_plan")
+        arr = (nv.SeqLaunch * max(1, n.value))()
+        nv.check(lib.rs_seqnet_launch_plan(self._h, int(B), int(L), int(ragged), arr, n.value, C.byref(n)), "rs_seqnet_launch_plan")
+        out = []
+        for e in arr[:n.value]:
+            d = {f: int(getattr(e, f)) for f, _ in nv.SeqLaunch._fields_}
+            d["family"] = nv.RS_SEQ_FAMILIES[d["family"]]
+            out.append(d)
+        return out
+
     @property
     def ragged_ok(self) -> bool:
         """True when forward_ragged can run this program (all of its ops inside fused launches: a ResNet's stem and blocks)"""

@@ -225,7 +225,7 @@ def test_modeldir_reads_a_cnn_rnn_config(tmp_path, golden_dir, monkeypatch, pars
             assert getattr(c.cnn_rnn, k) == cfg[k], k
 
 
-def test_abi_symbols_and_null_handles():
+def test_abi_2_9_symbols_and_null_handles():
     from riser_amd import _native as nv
     from riser_amd import build
     build.build()
@@ -233,7 +233,7 @@ def test_abi_symbols_and_null_handles():
     for s in ("rs_crnn_create", "rs_crnn_destroy", "rs_crnn_min_length", "rs_crnn_steps", "rs_crnn_workspace_bytes",
               "rs_crnn_max_batch", "rs_crnn_forward_ragged"):
         assert s in nv.SYMBOLS and hasattr(lib, s), s
-    assert lib.rs_version() == (2 << 16) | 8
+    assert lib.rs_version() == (2 << 16) | 9
     h = C.c_void_p()
     assert lib.rs_crnn_create(None, 1, None, 1, None, None, 2, 0, C.byref(h)) == nv.RS_ERR_ARG
     assert b"rs_crnn_create" in lib.rs_last_error()

@@ -48,11 +48,11 @@ def _inputs(L):
 
 
 # ------------------------------------------------------------------------------------------------ CPU
-def test_set_mode_and_tile_plan_abi_without_a_gpu():
+def test_set_mode_tile_plan_and_launch_plan_abi_without_a_gpu():
     import ctypes as C
     from riser_amd import _native as nv
     lib = nv.lib()
-    assert lib.rs_version() == (2 << 16) | 8
+    assert lib.rs_version() == (2 << 16) | 9
     assert lib.rs_tcn_set_mode(None, nv.RS_BF16X3) == nv.RS_ERR_ARG
     assert b"rs_tcn_set_mode" in lib.rs_last_error()
     assert lib.rs_tcn_set_mode(None, nv.RS_F32) == nv.RS_ERR_ARG
@@ -61,6 +61,14 @@ def test_set_mode_and_tile_plan_abi_without_a_gpu():
     assert lib.rs_tcn_tile_plan(None, 0, 1, 1, C.byref(t), C.byref(nb), C.byref(tiles)) == nv.RS_ERR_ARG
     assert b"rs_tcn_tile_plan" in lib.rs_last_error()
     assert (t.value, nb.value, tiles.value) == (-7, -7, -7)
+    # ABI 2.9: the conv program's launch-plan query refuses a null model, B < 1, an empty length and a NULL count (the
+    # length below a program's minimum is refused on the GPU, tests/test_resnet_shapes.py)
+    n = C.c_int32(-7)
+    for args in ((None, 1, 4000, 0, None, 0, C.byref(n)), (None, 0, 4000, 0, None, 0, C.byref(n)),
+                 (None, 1, 0, 1, None, 0, C.byref(n)), (None, 1, 4000, 0, None, 0, None)):
+        assert lib.rs_seqnet_launch_plan(*args) == nv.RS_ERR_ARG
+        assert b"rs_seqnet_launch_plan" in lib.rs_last_error()
+    assert n.value == -7
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -13,7 +13,7 @@ Reference entry points exercised:
   F2  Model.classify / ConvNet.forward        riser/model.py:22-28, riser/nets/cnn.py:43-65  (F2b: depth > 1 / odd kernels; F2c: `gap` head; F2d: `fc` head)
   F3  SequencerControl.target                 riser/control.py:11-124 (fake client)
   F4  SignalProcessor.get_polyA_end           riser/preprocess.py:42-79
-  F5  ResNet.forward                          riser/nets/resnet.py
+  F5  ResNet.forward                          riser/nets/resnet.py  (F5b: edge configs of the launch-form sweep)
   F6  TCN.forward / TCNBot.forward            riser/nets/tcn.py, riser/nets/tcn_bot.py  (F6b: edge configs)
   F7  ConvRecNet.forward                      riser/nets/cnn_rnn.py
 """
@@ -439,6 +439,65 @@ def f5_resnet():
     np.savez_compressed(os.path.join(OUT, "resnet.npz"), **out)
 
 
+# edge configs of tests/test_resnet_shapes.py (same names, configs and weight seed): each one a launch form of csrc/seqnet.hip
+_RB = lambda ch, bl, k, p, s, block="basic": dict(channels=ch, kernel=k, padding=p, stride=s, block=block, n_layers=len(ch),
+                                                  blocks=bl, n_classes=2)
+RESNET_EDGE_CFGS = {
+    "s1_w8_np56": _RB([12, 56], [1, 2], 19, 5, 3),           # stem nt 1, an 8-wave block, compact column pitch 56 < 64
+    "np40": _RB([44, 40], [1, 2], 9, 4, 2),                  # a 40-channel stage after a 44-channel one: pitch 40, not 48
+    "bneck_nto123": _RB([16, 32, 48], [1, 1, 1], 19, 5, 3, "bottleneck"),    # NTM 1 with NTO 1, 2, 3
+    "bneck_nto45": _RB([64, 66, 72], [1, 1, 1], 9, 4, 2, "bottleneck"),      # NTO 4, NTO 5 at NTM 1 and at NTM 2
+    "wide_stem": _RB([96, 40], [1, 1], 7, 3, 2),             # a stem wider than 80: unfused stem, pool and stage
+    "mixed": _RB([40, 36, 76], [1, 1, 1], 9, 4, 2),          # bf16x3 mixes split and fp32 blocks
+}
+RESNET_EDGE_SEED = 17
+
+
+def f5b_resnet_edges():
+    """reference ResNet (riser/nets/resnet.py) in eval mode on the edge configs of the launch-form sweep: logits and
+    probabilities of three synth reads at the program's minimum length, one more, 4097 and 16000.  The weights are not
+    stored: they are synth.make_resnet_state_dict(seed, cfg), loaded strictly into the reference's own module, and the cfg
+    records the seed and synth.state_dict_sha16 of them."""
+    from nets.resnet import ResNet
+    from riser_amd.resnet import build_program
+    out = {}
+    proc = SignalProcessor(Kit.create_from_version("RNA004"))
+    for name, cfg in RESNET_EDGE_CFGS.items():
+        net = ResNet(types.SimpleNamespace(**cfg))
+        sd = synth.make_resnet_state_dict(RESNET_EDGE_SEED, cfg)
+        new = {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+        for k, v in net.state_dict().items():
+            # the generator makes neither the BN counters nor the shortcut of a block that does not apply one (the reference
+            # builds it anyway, resnet.py:21-24, and its forward skips it, :40-47): the module's own values for those
+            if k not in new:
+                assert k.endswith("num_batches_tracked") or ".shortcut." in k, k
+                new[k] = v
+        net.load_state_dict(new, strict=True)
+        net.eval()
+        mn = 1
+        while True:                                         # the shortest read every conv and pool of the program accepts
+            try:
+                with torch.no_grad():
+                    net(torch.zeros((1, mn)))
+                break
+            except RuntimeError:
+                mn += 1
+        lens = (mn, mn + 1, 4097, 16000)
+        for L in lens:
+            sigs = synth.make_signals(SIG_SEED, 3, L, first_read=80)
+            x = np.stack([proc.mad_normalise(s.copy()) for s in sigs]).astype(np.float32)
+            with torch.no_grad():
+                logits = net(torch.from_numpy(x))
+                probs = torch.softmax(logits, dim=1)
+            out[f"{name}.L{L}.logits"] = logits.numpy()
+            out[f"{name}.L{L}.probs"] = probs.numpy()
+        build_program(sd, types.SimpleNamespace(**cfg))     # the state dict is one the program builder reads
+        out[f"{name}.cfg"] = np.array(json.dumps(dict(cfg, lengths=[int(v) for v in lens], seed=RESNET_EDGE_SEED,
+                                                      sd_sha16=synth.state_dict_sha16(sd))))
+        print("F5b:", name, "min", mn, out[f"{name}.L4097.probs"][:, 1])
+    np.savez_compressed(os.path.join(OUT, "resnet_edges.npz"), **out)
+
+
 TCN_CFGS = {
     # name: (bottleneck, config); n_filters 18 and 36 leave channel counts off the multiples of 4 (padding paths)
     "tcn_k3_b2": (False, dict(in_channels=1, n_filters=24, kernel=3, dilation=2, n_layers=5, dropout=0.2, n_classes=2)),
@@ -618,6 +677,8 @@ if __name__ == "__main__":
         f3_control()
     if "f5" in which:
         f5_resnet()
+    if "f5b" in which:
+        f5b_resnet_edges()
     if "f6" in which:
         f6_tcn()
     if "f6b" in which:
