@@ -18,8 +18,18 @@ CFG_KEYS = ("n_conv_layers", "channels", "kernels", "cell", "hidden", "n_rec_lay
 
 
 def tol(ref):
-    """the device's tolerance on a logit: 2e-5 relative above 1"""
-    return 2e-5 * np.maximum(1.0, np.abs(ref))
+    """the device's tolerance on a logit, relative above 1: 4x the largest gap measured on an MI355X over the eight configs of
+    this file, rounded up (the fixtures against the reference and float64, the ragged sweeps, the 512-read bench batches).
+    Measured, x max(1, |logit|): lstm_bi_r2 5.7e-8, gru_bi_r1_c1 2.8e-7, lstm_uni_r3 2.7e-8, gru_uni_r2_h130 4.0e-7,
+    lstm_bi_h130 4.0e-7, gru_bi_r2 3.4e-7, bench_lstm 7.4e-8, bench_gru 2.8e-7"""
+    return 2e-6 * np.maximum(1.0, np.abs(ref))
+
+
+def held(tag, got, ref):
+    """print the largest gap in units of max(1, |logit|), then hold every logit to tol()"""
+    err = np.abs(got - ref)
+    print(f"\nCRNN_GAP {tag} max|dev-ref|/scale {float((err / np.maximum(1.0, np.abs(ref))).max()):.3e}")
+    assert (err <= tol(ref)).all(), (tag, float(err.max()))
 
 
 def _load(golden_dir, name):
@@ -280,8 +290,8 @@ def test_model_matches_reference_and_float64(golden_dir, name):
         f64 = crnn_ref.forward(prog, x)
         probs, logits = m.classify_batch(x, return_logits=True)
         lg = logits.cpu().numpy()
-        assert (np.abs(lg - wl) <= tol(wl)).all(), (L, np.abs(lg - wl).max())
-        assert (np.abs(lg - f64) <= tol(f64)).all(), (L, np.abs(lg - f64).max())
+        held(f"{name} L{L} reference", lg, wl)
+        held(f"{name} L{L} float64", lg, f64)
         assert np.abs(probs.cpu().numpy() - wp).max() < 1e-5, L
         fb = m.forward_batch(torch.from_numpy(x).to(m.device), np.full(3, L, dtype=np.int32)).cpu().numpy()
         assert np.array_equal(fb, probs.cpu().numpy())
@@ -312,8 +322,7 @@ def test_ragged_sweep_against_float64_and_solo_runs(golden_dir, name):
     probs, logits = m.classify_batch(sigs, return_logits=True)
     logits = logits.cpu().numpy()
     want = crnn_ref.forward_ragged(prog, sigs)
-    err = np.abs(logits - want)
-    assert (err <= tol(want)).all(), (name, float(err.max()), lens[int(np.argmax(err.max(1)))])
+    held(f"{name} ragged float64", logits, want)
     for i, s in enumerate(sigs):
         _, l1 = m.classify_batch([s], return_logits=True)
         assert np.array_equal(logits[i], l1.cpu().numpy()[0]), (name, i, lens[i])
@@ -333,8 +342,7 @@ def test_bench_net_512_raw_reads(cell):
     probs, logits = m.classify_raw(sig, off, ln, lh, return_logits=True)
     x = np.stack([ro.mad_normalise(s) for s in sigs]).astype(np.float32)
     want = np.concatenate([crnn_ref.forward(prog, x[i:i + 128]) for i in range(0, 512, 128)])
-    err = np.abs(logits.cpu().numpy() - want)
-    assert (err <= tol(want)).all(), float(err.max())
+    held(f"bench_{cell} 512 float64", logits.cpu().numpy(), want)
     m.close()
 
 

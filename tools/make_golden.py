@@ -15,7 +15,7 @@ Reference entry points exercised:
   F4  SignalProcessor.get_polyA_end           riser/preprocess.py:42-79
   F5  ResNet.forward                          riser/nets/resnet.py  (F5b: edge configs of the launch-form sweep)
   F6  TCN.forward / TCNBot.forward            riser/nets/tcn.py, riser/nets/tcn_bot.py  (F6b: edge configs)
-  F7  ConvRecNet.forward                      riser/nets/cnn_rnn.py
+  F7  ConvRecNet.forward                      riser/nets/cnn_rnn.py  (F7b: edge configs of the shape sweep)
 """
 import json
 import logging
@@ -655,6 +655,42 @@ def f7_crnn():
     np.savez_compressed(os.path.join(OUT, "crnn.npz"), **out)
 
 
+def f7b_crnn_edges():
+    """F7 at the edges of the device program's shape arithmetic, on six configs of tests/test_crnn_shapes.py (taken from
+    there with their seeds, so the two cannot drift apart): taps 1 and 2, a 19-tap kernel over 8 channels, six conv layers,
+    13 / 100 / 130 output channels, hidden 5, 129 and 320.  Logits and probabilities of three synth reads at the minimum
+    length, one more, an odd-pool length and 4097; prints the largest gap to the float64 forward of tests/crnn_ref.py."""
+    from nets.cnn_rnn import ConvRecNet
+    from riser_amd import crnn as R
+    from tests import crnn_ref
+    from tests import test_crnn_shapes as S
+    out, worst = {}, 0.0
+    proc = SignalProcessor(Kit.create_from_version("RNA004"))
+    for name in S.EDGES:
+        cfg, seed = S.CONFIGS[name], S.SEED[name]
+        net = ConvRecNet(types.SimpleNamespace(**cfg))
+        sd = synth.make_crnn_state_dict(seed, cfg, gain=S.GAIN)
+        net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+        net.eval()
+        prog = R.build_crnn_program(sd, types.SimpleNamespace(**cfg))
+        lens = S.edge_lengths(prog)
+        assert lens[0] == crnn_min_length(cfg["kernels"])
+        for L in lens:
+            sigs = synth.make_signals(SIG_SEED, 3, L, first_read=60)
+            x = np.stack([proc.mad_normalise(s.copy()) for s in sigs]).astype(np.float32)
+            with torch.no_grad():
+                logits = net(torch.from_numpy(x))
+                probs = torch.softmax(logits, dim=1)
+            out[f"{name}.L{L}.logits"] = logits.numpy()
+            out[f"{name}.L{L}.probs"] = probs.numpy()
+            gap = float(np.abs(crnn_ref.forward(prog, x) - logits.numpy()).max())
+            worst = max(worst, gap)
+        out[f"{name}.cfg"] = np.array(json.dumps(dict(cfg, lengths=[int(v) for v in lens], seed=seed, gain=S.GAIN,
+                                                      sd_sha16=synth.state_dict_sha16(sd))))
+        print("F7b:", name, "min", lens[0], out[f"{name}.L4097.probs"][:, 1], "float64 gap so far %.2e" % worst)
+    np.savez_compressed(os.path.join(OUT, "crnn_edges.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -685,3 +721,5 @@ if __name__ == "__main__":
         f6b_tcn_edges()
     if "f7" in which:
         f7_crnn()
+    if "f7b" in which:
+        f7b_crnn_edges()
