@@ -66,7 +66,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), lib_name: 
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
+    headers = [os.path.join(d, f) for d, _, fs in os.walk(CSRC) for f in fs if f.endswith((".hpp", ".h"))]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "riser_amd.h"))
     headers.append(os.path.abspath(__file__))
     jobs = []
