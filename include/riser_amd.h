@@ -481,6 +481,19 @@ RS_API int rs_crnn_max_batch(const rs_crnn* m, int ld);
  * d_logits may be null. */
 RS_API int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x /* fp32 [B, ld] */, const int32_t* d_len, int B, int ld,
                                   void* d_ws, size_t ws_bytes, float* d_probs /* [B, 2] */, float* d_logits, void* stream);
+/* Added after ABI 2.9 (rs_version stays 2.9): arithmetic of the gate GEMMs whose input is a hidden state - the recurrence
+ * h_{t-1} W_hh^T of every layer and direction, and the input projection of every layer but the first.  RS_F16X3 runs them in
+ * split precision on the f16 MFMA (csrc/crnn/x3.hpp): hi = f16(v), lo = f16(v - hi), a product is hi*hi + lo*hi + hi*lo on
+ * three v_mfma_f32_16x16x32_f16 with fp32 accumulation.  The conv front, the first layer's projection (its input is the conv
+ * output, unbounded), the gate non-linearities, c, the GRU update, the head stay fp32.  A hidden state lies in (-1, 1) and the
+ * weights are packed with an exact power-of-two scale per matrix, so no f16 operand can overflow: the mode has no range check
+ * and no saturation flag.  RS_F32 / RS_F32W go back to fp32 (the default), whose bits are those of a freshly created handle.
+ * Any other dtype, or a null handle, returns RS_ERR_ARG and leaves the mode as it was; so does RS_F16X3 for a recurrent
+ * weight that is not finite.  The f16 weights are packed on the first switch to RS_F16X3 and freed by rs_crnn_destroy.  Both
+ * modes use the same fp32 activation buffers: rs_crnn_workspace_bytes and rs_crnn_max_batch report the same figures in
+ * either.  A read in a ragged batch gets the bits it gets alone in either mode.  Not safe to call while a forward of the
+ * handle is being enqueued. */
+RS_API int rs_crnn_set_mode(rs_crnn* m, int dtype /* rs_dtype */);
 
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path

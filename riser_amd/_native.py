@@ -29,7 +29,7 @@ SYMBOLS = (
     "rs_tcn_create", "rs_tcn_destroy", "rs_tcn_receptive_field", "rs_tcn_workspace_bytes", "rs_tcn_max_batch", "rs_tcn_forward_ragged", "rs_tcn_set_mode",
     "rs_tcn_tile_plan",
     "rs_crnn_create", "rs_crnn_destroy", "rs_crnn_min_length", "rs_crnn_steps", "rs_crnn_workspace_bytes", "rs_crnn_max_batch",
-    "rs_crnn_forward_ragged",
+    "rs_crnn_forward_ragged", "rs_crnn_set_mode",
 )
 
 
@@ -163,6 +163,8 @@ def lib():
     L.rs_crnn_max_batch.argtypes = [vp, i32]
     L.rs_crnn_forward_ragged.restype = i32
     L.rs_crnn_forward_ragged.argtypes = [vp, vp, vp, i32, i32, vp, sz, vp, vp, vp]
+    L.rs_crnn_set_mode.restype = i32
+    L.rs_crnn_set_mode.argtypes = [vp, i32]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32

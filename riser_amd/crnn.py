@@ -136,14 +136,19 @@ class _Layer(C.Structure):
 
 
 class CRNNNet:
-    """A ConvRecNet on the device (rs_crnn_*): the surface Model drives for SeqNet - forward, forward_ragged, max_batch."""
+    """A ConvRecNet on the device (rs_crnn_*): the surface Model drives for SeqNet - forward, forward_ragged, max_batch.
+    dtype "f32" (also "f32w" / "fp32": fp32 on the f32-input MFMA, the default) or "f16x3": the gate GEMMs whose input is a
+    hidden state (every recurrence, the input projection of every layer but the first) in split precision on the f16 MFMA,
+    everything else fp32 (rs_crnn_set_mode).  A hidden state lies in (-1, 1) and the weights are packed with a power-of-two
+    scale, so no f16 operand can overflow: the mode has no range check and never reports saturation."""
 
     ragged_ok = True
 
     def __init__(self, prog, device, dtype: str = "f32"):
-        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32"}.get(dtype)
+        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32", "f16x3": "f16x3"}.get(dtype)
         if self.dtype is None:
-            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) only")
+            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'f16x3' "
+                             "(split precision on the f16 MFMA for the gate GEMMs of hidden states)")
         nv.require_gpu()
         d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
@@ -166,6 +171,16 @@ class CRNNNet:
                  "rs_crnn_create")
         self._h = h
         self._ws = None
+        if self.dtype == "f16x3":
+            self.set_mode("f16x3")
+
+    def set_mode(self, dtype: str):
+        """switch the arithmetic of the hidden-state gate GEMMs between forwards: "f32" or "f16x3" (rs_crnn_set_mode)"""
+        code = {"f32": nv.RS_F32, "f32w": nv.RS_F32W, "fp32": nv.RS_F32, "f16x3": nv.RS_F16X3}.get(dtype)
+        if code is None:
+            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' or 'f16x3'")
+        nv.check(nv.lib().rs_crnn_set_mode(self._h, code), "rs_crnn_set_mode")
+        self.dtype = "f16x3" if code == nv.RS_F16X3 else "f32"
 
     @property
     def min_length(self) -> int:

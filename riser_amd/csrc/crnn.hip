@@ -22,18 +22,25 @@
 // Every output element comes from a fixed k-ordered MFMA sequence whatever the batch, the tile or ld, so a read gets the
 // bits it gets alone.  The K order of the projection and the recurrence: at k-step s lane (r, q) holds
 // k = 16 (s / 4) + 4 q + s % 4, so that a lane reads its A operand as one float4 per four steps.
+//
+// rs_crnn_set_mode(RS_F16X3) switches the gate GEMMs whose input is a hidden state - every recurrence and the input projection
+// of every layer but the first - to split precision on the f16 MFMA (crnn/x3.hpp); the kernels above and their launch order
+// are the fp32 mode's and do not change with it.
 #include "common.hpp"
+#include "crnn/shared.hpp"
+#include "crnn/x3.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <new>
+#include <vector>
 
 namespace rs {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kMaxConv = 16;
 constexpr int kConvRows = 64;                       // conv positions per workgroup (32 pooled)
 constexpr int kConvLds = 64 * 1024;
 constexpr int kResHidden = 128;                     // hidden sizes up to this keep W_hh in VGPRs
@@ -44,20 +51,6 @@ inline int cp4(int c) { return (c + 3) & ~3; }
 inline int p16(int c) { return (c + 15) & ~15; }
 inline int lds_pitch(int cp) { return ((cp / 4) % 2 == 0) ? cp + 4 : cp; }
 
-struct Lens {
-    int n;                      // conv layers
-    int k[kMaxConv];
-};
-
-// samples of read b after `upto` conv layers; 0 where the reference's conv or max_pool would raise
-__device__ __forceinline__ int crnn_len(const int32_t* len, int b, int ld, const Lens& ls, int upto) {
-    int L = as_const_len(len)[b];
-    L = L < 0 ? 0 : (L > ld ? ld : L);
-    for (int i = 0; i < upto; ++i) L = L >= ls.k[i] + 1 ? (L - ls.k[i] + 1) >> 1 : 0;
-    return L;
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------------------ conv front
 struct ConvArgs {
@@ -378,6 +371,14 @@ struct LayerDev {
     float* bias[2] = {nullptr, nullptr};    // [N]
     float* whh[2] = {nullptr, nullptr};     // packed [N / 16][KSh][64]
     float* bhn[2] = {nullptr, nullptr};     // [Hp]
+    // f16x3 mode: the host weights and their f16 hi / lo fragments.  The host copies (W_hh, and W_ih of every layer but the
+    // first: 4 bytes per weight, 1.6 MB for the bench LSTM) wait for the first rs_crnn_set_mode(RS_F16X3), which packs and
+    // releases them; a handle that never leaves fp32 keeps them until rs_crnn_destroy
+    std::vector<float> h_wih[2], h_whh[2];
+    u32x4* wih3[2] = {nullptr, nullptr};    // packed [N / 16][KSi3][hi, lo][64]; null for the first layer (fp32 projection)
+    u32x4* whh3[2] = {nullptr, nullptr};    // packed [N / 16][KSh3][hi, lo][64]
+    float inv_si[2] = {1.0f, 1.0f}, inv_sh[2] = {1.0f, 1.0f};
+    int KSi3 = 0, KSh3 = 0;
 };
 
 template <class T>
@@ -414,6 +415,8 @@ struct rs_crnn {
     float* d_fcb = nullptr;
     int out_dim = 0;
     int min_len = 1;
+    int x3 = 0;                 // 1: RS_F16X3
+    bool x3_packed = false;
 };
 
 namespace rs {
@@ -470,6 +473,8 @@ int rs_crnn_destroy(rs_crnn* m) {
             if (l.bias[d]) (void)hipFree(l.bias[d]);
             if (l.whh[d]) (void)hipFree(l.whh[d]);
             if (l.bhn[d]) (void)hipFree(l.bhn[d]);
+            if (l.wih3[d]) (void)hipFree(l.wih3[d]);
+            if (l.whh3[d]) (void)hipFree(l.whh3[d]);
         }
     if (m->d_fcw) (void)hipFree(m->d_fcw);
     if (m->d_fcb) (void)hipFree(m->d_fcb);
@@ -558,6 +563,8 @@ int rs_crnn_create(const rs_crnn_conv* convs, int n_conv, const rs_crnn_layer* l
         ld.N = ng * ld.Hp;
         ld.KSi = p16(s.in_dim) / 4;
         ld.KSh = ld.Hp / 4;
+        ld.KSi3 = p32(s.in_dim) / 32;
+        ld.KSh3 = p32(ld.Hp) / 32;
         m->layers.push_back(ld);
         LayerDev& L = m->layers.back();
         for (int d = 0; d < L.ndir && e == hipSuccess; ++d) {
@@ -572,6 +579,8 @@ int rs_crnn_create(const rs_crnn_conv* convs, int n_conv, const rs_crnn_layer* l
             if (e == hipSuccess) e = upload(&L.whh[d], pack_gates(s.w_hh[d], ng, L.H, L.Hp, L.H));
             if (e == hipSuccess) e = upload(&L.bias[d], bias);
             if (e == hipSuccess) e = upload(&L.bhn[d], bhn);
+            if (l > 0) L.h_wih[d].assign(s.w_ih[d], s.w_ih[d] + (size_t)ng * L.H * L.in_dim);
+            L.h_whh[d].assign(s.w_hh[d], s.w_hh[d] + (size_t)ng * L.H * L.H);
         }
     }
     if (e == hipSuccess) e = upload(&m->d_fcw, std::vector<float>(fc_w, fc_w + 2 * (size_t)out_dim));
@@ -585,6 +594,62 @@ int rs_crnn_create(const rs_crnn_conv* convs, int n_conv, const rs_crnn_layer* l
     for (int i = n_conv - 1; i >= 0; --i) need = 2 * need + m->convs[i].k - 1;
     m->min_len = (int)std::min<int64_t>(need, INT32_MAX);
     *out = m;
+    return RS_OK;
+}
+
+int rs_crnn_set_mode(rs_crnn* m, int dtype) {
+    if (!m) {
+        set_error("rs_crnn_set_mode: null handle");
+        return RS_ERR_ARG;
+    }
+    if (dtype == RS_F32 || dtype == RS_F32W) {
+        m->x3 = 0;
+        return RS_OK;
+    }
+    if (dtype != RS_F16X3) {
+        set_error("rs_crnn_set_mode: dtype %d: a CNN-RNN runs in RS_F32 / RS_F32W or RS_F16X3", dtype);
+        return RS_ERR_ARG;
+    }
+    if (!m->x3_packed) {
+        DeviceGuard guard(m->device);
+        RS_HIP(guard.err);
+        // pack everything on the host first: a refusal leaves the handle as it was
+        struct Packed {
+            std::vector<uint32_t> wih[2], whh[2];
+            float inv_si[2], inv_sh[2];
+        };
+        std::vector<Packed> pk(m->layers.size());
+        for (size_t l = 0; l < m->layers.size(); ++l) {
+            const LayerDev& L = m->layers[l];
+            const int ng = L.gru ? 3 : 4;
+            for (int d = 0; d < L.ndir; ++d) {
+                bool ok = pack_gates_x3(L.h_whh[d].data(), ng, L.H, L.Hp, L.H, pk[l].whh[d], pk[l].inv_sh[d]);
+                if (ok && l > 0) ok = pack_gates_x3(L.h_wih[d].data(), ng, L.H, L.Hp, L.in_dim, pk[l].wih[d], pk[l].inv_si[d]);
+                if (!ok) {
+                    set_error("rs_crnn_set_mode: recurrent layer %d has a weight that is not finite", (int)l);
+                    return RS_ERR_ARG;
+                }
+            }
+        }
+        hipError_t e = hipSuccess;
+        for (size_t l = 0; l < m->layers.size() && e == hipSuccess; ++l) {
+            LayerDev& L = m->layers[l];
+            for (int d = 0; d < L.ndir && e == hipSuccess; ++d) {
+                if (!L.whh3[d]) e = upload(reinterpret_cast<uint32_t**>(&L.whh3[d]), pk[l].whh[d]);
+                if (e == hipSuccess && l > 0 && !L.wih3[d]) e = upload(reinterpret_cast<uint32_t**>(&L.wih3[d]), pk[l].wih[d]);
+                L.inv_sh[d] = pk[l].inv_sh[d];
+                if (l > 0) L.inv_si[d] = pk[l].inv_si[d];
+            }
+        }
+        if (e != hipSuccess) return hip_fail(e, "rs_crnn_set_mode upload");
+        m->x3_packed = true;
+        for (LayerDev& L : m->layers)               // the host copies have served
+            for (int d = 0; d < 2; ++d) {
+                std::vector<float>().swap(L.h_wih[d]);
+                std::vector<float>().swap(L.h_whh[d]);
+            }
+    }
+    m->x3 = 1;
     return RS_OK;
 }
 
@@ -729,7 +794,29 @@ int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x, const int32_t* d_len, i
                 set_error("rs_crnn_forward_ragged: grid too large: split the batch");
                 return RS_ERR_ARG;
             }
-            hipLaunchKernelGGL(crnn_proj_kernel, dim3((unsigned)gx, (unsigned)((L.N / 16 + 3) / 4)), dim3(256), 0, st, a);
+            if (m->x3 && l > 0) {                   // the input is a previous layer's h
+                ProjX3Args x;
+                memset(&x, 0, sizeof(x));
+                x.a = a.a;
+                x.M = a.M;
+                x.a_pitch = a.a_pitch;
+                x.K = a.K;
+                x.KS = L.KSi3;
+                x.last_only = a.last_only;
+                x.T_ld = T;
+                x.B = B;
+                x.ld = ld;
+                x.len = d_len;
+                x.ls = m->ls;
+                x.w = L.wih3[d];
+                x.bias = L.bias[d];
+                x.inv_s = L.inv_si[d];
+                x.y = xp[d];
+                x.N = L.N;
+                hipLaunchKernelGGL(crnn_proj_x3_kernel, dim3((unsigned)gx, (unsigned)((L.N / 16 + 15) / 16)), dim3(256), 0, st, x);
+            } else {
+                hipLaunchKernelGGL(crnn_proj_kernel, dim3((unsigned)gx, (unsigned)((L.N / 16 + 3) / 4)), dim3(256), 0, st, a);
+            }
             RS_HIP(hipGetLastError());
             r.xp[d] = xp[d];
             r.xp_rows[d] = one ? 1 : T;
@@ -756,7 +843,40 @@ int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x, const int32_t* d_len, i
         r.ls = m->ls;
         const dim3 grid((unsigned)((B + 15) / 16), (unsigned)L.ndir);
         const size_t lds = (size_t)48 * r.hpitch * 4;
-        if (L.H <= kResHidden)
+        if (m->x3) {
+            RecX3Args x;
+            memset(&x, 0, sizeof(x));
+            for (int d = 0; d < L.ndir; ++d) {
+                x.xp[d] = r.xp[d];
+                x.xp_rows[d] = r.xp_rows[d];
+                x.one_step[d] = r.one_step[d];
+                x.whh[d] = L.whh3[d];
+                x.inv_s[d] = L.inv_sh[d];
+                x.bhn[d] = L.bhn[d];
+            }
+            x.y = r.y;
+            x.fin = r.fin;
+            x.T_ld = T;
+            x.y_pitch = r.y_pitch;
+            x.fin_pitch = r.fin_pitch;
+            x.B = B;
+            x.ld = ld;
+            x.gru = L.gru;
+            x.H = L.H;
+            x.Hp = L.Hp;
+            x.HT = L.HT;
+            x.KS = L.KSh3;
+            x.N = L.N;
+            x.relu = L.relu;
+            x.hp = 32 * L.KSh3 + 8;
+            x.len = d_len;
+            x.ls = m->ls;
+            const size_t lds3 = (size_t)4 * 16 * x.hp * 2;      // two buffers of an f16 hi and an f16 lo plane
+            if (L.H <= kResHidden)
+                hipLaunchKernelGGL(crnn_rec_x3_kernel<true>, grid, dim3(512), lds3, st, x);
+            else
+                hipLaunchKernelGGL(crnn_rec_x3_kernel<false>, grid, dim3(512), lds3, st, x);
+        } else if (L.H <= kResHidden)
             hipLaunchKernelGGL(crnn_rec_kernel<true>, grid, dim3(512), lds, st, r);
         else
             hipLaunchKernelGGL(crnn_rec_kernel<false>, grid, dim3(512), lds, st, r);

@@ -1,5 +1,7 @@
 // MFMA operand vectors and the bf16 SPLIT of fp32 operands (hi = bf16(v), lo = bf16(v - hi); a product is hi*hi + lo*hi + hi*lo
 // on three v_mfma_f32_16x16x32_bf16 with fp32 accumulate): shared by the split-precision kernels of seqnet.hip and tcn_x3.hip.
+// The f16 twins (split2_f16 / mfma_f16 / mfma_x3_f16 on v_mfma_f32_16x16x32_f16) serve crnn/x3.hpp, whose split operands are
+// bounded (hidden states) or scaled by the packer (weights): f16's range of 65504 is the caller's business.
 #pragma once
 #include "../common.hpp"
 
@@ -33,6 +35,26 @@ __device__ __forceinline__ f32x4 mfma_x3(const u32x4& ah, const u32x4& al, const
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ah), __builtin_bit_cast(bf16x8_t, bh), c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, al), __builtin_bit_cast(bf16x8_t, bh), c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ah), __builtin_bit_cast(bf16x8_t, bl), c, 0, 0, 0);
+}
+
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+
+// two fp32 -> their f16 hi parts and the f16 roundings of the residuals
+__device__ __forceinline__ void split2_f16(float a, float b, unsigned& hi, unsigned& lo) {
+    const _Float16 ha = (_Float16)a, hb = (_Float16)b;
+    const f16x2_t h = {ha, hb};
+    const f16x2_t l = {(_Float16)(a - (float)ha), (_Float16)(b - (float)hb)};
+    hi = __builtin_bit_cast(unsigned, h);
+    lo = __builtin_bit_cast(unsigned, l);
+}
+__device__ __forceinline__ f32x4 mfma_f16(const u32x4& a, const u32x4& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma_x3_f16(const u32x4& ah, const u32x4& al, const u32x4& bh, const u32x4& bl, f32x4 c) {
+    c = mfma_f16(ah, bh, c);
+    c = mfma_f16(al, bh, c);
+    return mfma_f16(ah, bl, c);
 }
 }  // namespace
 }  // namespace rs

@@ -65,7 +65,10 @@ class Model:
         that stays within 1e-3 of the reference), "f16xf8" (f16x3 whose wide layers evaluate the two cross terms of the
         split product as one block-scaled e4m3 product on the 8-bit MFMA: two instruction times per product instead of
         three, within ~3e-4 of the reference), "f16" / "bf16" (plain 16-bit activations and weights, fp32
-        accumulate: fast, approximate).
+        accumulate: fast, approximate).  A CNN-RNN (`model: cnn-rnn`) takes "f32w" / "f32" (the same fp32 program) or
+        "f16x3": there the split runs on the gate GEMMs whose input is a hidden state (every recurrence and the input
+        projection of every layer but the first), whose operands are bounded, so that mode has no range check and
+        `saturated()` is always False for it.
         range_check (half-precision modes only): run a small synthetic sample through the new model and REFUSE (ValueError)
         when an activation comes within a factor of 4 of half precision's 65504 - those modes cannot represent larger
         activations, the reference's fp32 path can (riser/model.py:22-28).  RS_RANGE_CHECK=0 or range_check=False skip it;
@@ -321,8 +324,9 @@ class Model:
 
     def _init_crnn(self, state, cc, dtype: str):
         from .crnn import CRNNNet, build_crnn_program
-        if dtype not in ("f32w", "f32"):
-            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) only")
+        if dtype not in ("f32w", "f32", "f16x3"):
+            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'f16x3' "
+                             "(split precision on the f16 MFMA for the gate GEMMs of hidden states)")
         sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
         prog = build_crnn_program(sd, cc)
         self.classifier, self._fc_positions = "gap_fc", 0
