@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
+#include <string.h>
 
 #include <utility>
 #include <vector>
@@ -80,11 +82,39 @@ struct Hooks {
     int thin_h16_rows = -1;          // RS_THIN_H16_ROWS: split-precision layers of a launch with at most this many input rows run the
                                      // thin-launch kernel (conv_thin_h16.hip; 0 = never; default -1: by the cost estimates)
     bool x3_tail = true;             // RS_X3_TAIL=0: split-precision layers whose last panel holds <= 8 channels keep it as three 32-wide K steps instead of ONE merged step (conv_ring_h16.hip: TAIL)
-    int f8_min_cin = 200;            // RS_F8_MIN_CIN: RS_F16XF8 puts a layer on the 8-bit kernel from this many input channels on (api.hip: f8_eligible)
+    int f8_min_cin = 200;            // RS_F8_MIN_CIN: RS_F16XF8 puts a layer on the 8-bit kernel from this many input channels on (convnet_pack.hpp: f8_eligible)
     bool h16_wres = true;            // RS_H16_WRES=0: narrow 16-bit layers on the ring kernel instead of the weights-resident one
+    char plan_kc[128] = "";          // RS_PLAN_KC "layer:kc;...": forces the channel chunk of an F(4,3) layer (convnet_model.hpp: plan_static_wino4)
+    char x3_terms[128] = "";         // RS_X3_TERMS "layer:mask;...": -DRS_X3_MASK measurement builds only (ConvLayerDev::x3_terms)
+    bool wino4_set = false;          // RS_WINO4: comma list of the layers that run F(4,3) ("none": F(2,3) everywhere), instead of
+    char wino4[128] = "";            // the rule of convnet_model.hpp: use_wino4
     static Hooks from_env();
 };
 const Hooks& default_hooks();
+
+// The per-layer switches are lists "layer:value;..." or "layer:wm,wn,mt,nt;...".  The next entry of `layer` in the list from q
+// on: its numbers in v, and the text behind it to go on from (null: there is no further entry).  Where a layer is named more
+// than once its users take the last entry that suits them, so they ask until the answer is null.
+inline const char* next_layer_value(const char* q, int layer, int* v) {
+    for (; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr) {
+        int l, x;
+        if (sscanf(q, "%d:%d", &l, &x) == 2 && l == layer) {
+            *v = x;
+            return strchr(q, ';') ? strchr(q, ';') + 1 : q + strlen(q);
+        }
+    }
+    return nullptr;
+}
+inline const char* next_layer_shape(const char* q, int layer, int* wm, int* wn, int* mt, int* nt) {
+    for (; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr) {
+        int l, x[4];
+        if (sscanf(q, "%d:%d,%d,%d,%d", &l, &x[0], &x[1], &x[2], &x[3]) == 5 && l == layer) {
+            *wm = x[0], *wn = x[1], *mt = x[2], *nt = x[3];
+            return strchr(q, ';') ? strchr(q, ';') + 1 : q + strlen(q);
+        }
+    }
+    return nullptr;
+}
 
 inline bool is_x3(int dtype) { return dtype == RS_BF16X3 || dtype == RS_F16X3 || dtype == RS_F16XF8; }
 inline bool is_f16_family(int dtype) { return dtype == RS_F16 || dtype == RS_F16X3 || dtype == RS_F16XF8; }

@@ -518,14 +518,13 @@ int launch_conv_f32(const ConvLayerDev& L, const float* d_x, float* d_y, const i
     }
     const int n16 = round_up(L.c_out, 16) / 16;
     const Shape* s = choose_shape(rows64, n16, p.kc, p.nch, num_cu, nullptr);
-    if (const char* force = L.hooks->force_f32; *force) {         // tuning aid: "layer:wm,wn,mt,nt;..."
-        int l, wm, wn, mt, nt;
-        for (const char* q = force; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr)
-            if (sscanf(q, "%d:%d,%d,%d,%d", &l, &wm, &wn, &mt, &nt) == 5 && l == layer_index)
-                for (int k = 0; k < kNumShapes; ++k)
-                    if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                        lds_bytes(kShapes[k], p.kc) <= 160 * 1024)
-                        s = &kShapes[k];
+    {   // tuning aid: "layer:wm,wn,mt,nt;..."
+        int wm, wn, mt, nt;
+        for (const char* q = L.hooks->force_f32; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
+            for (int k = 0; k < kNumShapes; ++k)
+                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
+                    lds_bytes(kShapes[k], p.kc) <= 160 * 1024)
+                    s = &kShapes[k];
     }
     if (!s) {
         set_error("conv_f32: no tile shape fits (kc=%d)", p.kc);

@@ -11,7 +11,7 @@
 // is ONE v_mfma_scale_f32_16x16x128_f8f6f4 per 64 input channels and tap: per 64 K two f16 instructions (32 cycles) and one
 // 8-bit instruction (32 cycles) where split precision issues six (96 cycles).
 //
-// Layout ("F8 rows"; api.hip: RS_F16XF8).  A row is a sequence of 128-byte panels, two per 64 channels:
+// Layout ("F8 rows"; convnet_pack.hpp: row_pitch, F8Layout).  A row is a sequence of 128-byte panels, two per 64 channels:
 //     H panel   hi16 x 64                                                  (the plain 16-bit panel of conv_ring_h16.hip)
 //     F panel   [hi8 c0-31 | lo8 c0-31 | hi8 c32-63 | lo8 c32-63]           activations
 //               [lo8 c0-31 | hi8 c0-31 | lo8 c32-63 | hi8 c32-63]           weights (so that unit k of A meets unit k of B)
@@ -67,7 +67,7 @@ constexpr int kThreads = 512;
 constexpr int kRowB = 128;                      // bytes of an LDS row (one panel)
 constexpr int kPieceRows = 1024 / kRowB;        // rows per DMA piece (one wave instruction)
 constexpr unsigned kOob = 0x80000000u;
-// E8M0 bytes of the weight planes (api.hip packs hi8 = e4m3(hi 2^-6), lo8 = e4m3(lo 2^5))
+// E8M0 bytes of the weight planes (convnet_pack.hpp: F8Layout packs hi8 = e4m3(hi 2^-6), lo8 = e4m3(lo 2^5))
 constexpr int kWScaleHi = 127 + 6, kWScaleLo = 127 - 5;
 
 struct F8Args {
@@ -781,14 +781,13 @@ int launch_conv_ring_f8(const ConvLayerDev& L, const void* d_x, void* d_y, const
     const int cols_cover = out_f8 ? cols_out : round_up(L.c_out, 16);
     const int n_panels = L.ring_panels;
     const Shape* s = choose_shape(rows64, cols_cover, n_panels, num_cu, in_f8);
-    if (const char* force = L.hooks->force_ring; *force) {          // tuning aid: "layer:wm,wn,mt,nt;..."
-        int l, wm, wn, mt, nt;
-        for (const char* q = force; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr)
-            if (sscanf(q, "%d:%d,%d,%d,%d", &l, &wm, &wn, &mt, &nt) == 5 && l == layer_index)
-                for (int k = 0; k < kNumShapes; ++k)
-                    if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                        lds_bytes(kShapes[k], in_f8) <= 160 * 1024)
-                        s = &kShapes[k];
+    {   // tuning aid: "layer:wm,wn,mt,nt;..."
+        int wm, wn, mt, nt;
+        for (const char* q = L.hooks->force_ring; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
+            for (int k = 0; k < kNumShapes; ++k)
+                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
+                    lds_bytes(kShapes[k], in_f8) <= 160 * 1024)
+                    s = &kShapes[k];
     }
     if (const int k = tuned_shape(L, rows64); k >= 0 && conv_ring_f8_shape_ok(L, k)) s = &kShapes[k];
     if (!s) {

@@ -812,16 +812,15 @@ int launch_conv_ring_h16(const ConvLayerDev& L, const void* d_x, void* d_y, cons
     double single_cost = 0.0;
     const Shape* s = choose_shape(rows64, n16, n_panels, num_cu, x3, &single_cost, tail);
     bool pinned = false;                                            // a forced or tuned shape runs as one launch
-    if (const char* force = L.hooks->force_ring; *force) {          // tuning aid: "layer:wm,wn,mt,nt;..."
-        int l, wm, wn, mt, nt;
-        for (const char* q = force; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr)
-            if (sscanf(q, "%d:%d,%d,%d,%d", &l, &wm, &wn, &mt, &nt) == 5 && l == layer_index)
-                for (int k = 0; k < kNumShapes; ++k)
-                    if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                        conv_ring_shape_ok(L, k)) {
-                        s = &kShapes[k];
-                        pinned = true;
-                    }
+    {   // tuning aid: "layer:wm,wn,mt,nt;..."
+        int wm, wn, mt, nt;
+        for (const char* q = L.hooks->force_ring; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
+            for (int k = 0; k < kNumShapes; ++k)
+                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
+                    conv_ring_shape_ok(L, k)) {
+                    s = &kShapes[k];
+                    pinned = true;
+                }
     }
     if (const int k = tuned_shape(L, rows64); k >= 0 && conv_ring_shape_ok(L, k)) {
         s = &kShapes[k];

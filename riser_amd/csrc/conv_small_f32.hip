@@ -21,7 +21,7 @@
 // The MFMA sequence per accumulator (chunk order, k-step order, operand roles, the Winograd input and output transforms
 // and every rounding in them) is that of the tiled kernels, so the results are BIT-IDENTICAL to theirs: a read classified
 // alone equals its row of a 512-read batch (tests/test_gpu_small.py).  The launch planner picks this kernel when the
-// launch has at most kSmallMaxWaves tiles (api.hip); layers 0 + 1 keep the streaming kernel.
+// launch has at most kSmallMaxWaves tiles (convnet_forward.hpp: select_kernel); layers 0 + 1 keep the streaming kernel.
 #include "common.hpp"
 
 #include <algorithm>

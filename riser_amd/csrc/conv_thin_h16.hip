@@ -15,7 +15,7 @@
 //     of ~350 cycles;
 //   * per accumulator the MFMAs run panel by panel, tap by tap, hi*hi, lo*hi, hi*lo - the ring kernel's order - and the epilogue
 //     is its arithmetic: BIT-IDENTICAL results (tests/test_gpu_small.py), a read alone equals its row of a 512-read batch.
-// One workgroup per tile, no tile walk (a thin launch is tens to hundreds of tiles).  The launch planner (api.hip) takes this
+// One workgroup per tile, no tile walk (a thin launch is tens to hundreds of tiles).  The launch planner (convnet_forward.hpp: select_kernel) takes this
 // kernel where its estimate beats the ring's.
 #include "common.hpp"
 

@@ -182,7 +182,7 @@ const Shape* choose_shape(int64_t rows_out, int n16, int kc, int nch, int num_cu
 }  // namespace
 
 int conv_wino_max_bn() { return 256; }
-// planner's estimate (SIMD cycles) of one launch with the best tile shape (compared with the small-batch kernel's in api.hip)
+// planner's estimate (SIMD cycles) of one launch with the best tile shape (compared with the small-batch kernel's in convnet_forward.hpp: select_kernel)
 double conv_wino_plan_cost(int64_t rows_out, int n16, int kc, int nch, int num_cu) {
     double cost = 1e300;
     choose_shape(rows_out, n16, kc, nch, num_cu, &cost, nullptr, false);
@@ -228,17 +228,16 @@ int launch_conv_wino(const ConvLayerDev& L, const float* d_x, float* d_y, const 
     int per_cu = 1;
     const Shape* s = choose_shape(rows64 / 2, n16, p.kc, p.nch, num_cu, &single_cost, &per_cu);
     bool pinned = false;                                          // a forced, fused or tuned shape runs as one launch
-    if (const char* force = L.hooks->force_wino; *force) {        // tuning aid: "layer:wm,wn,mt,nt;..."
-        int l, wm, wn, mt, nt;
-        for (const char* q = force; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr)
-            if (sscanf(q, "%d:%d,%d,%d,%d", &l, &wm, &wn, &mt, &nt) == 5 && l == layer_index)
-                for (int k = 0; k < kNumShapes; ++k)
-                    if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                        lds_bytes(kShapes[k], p.kc) <= 160 * 1024) {
-                        s = &kShapes[k];
-                        pinned = true;
-                        per_cu = 1;
-                    }
+    {   // tuning aid: "layer:wm,wn,mt,nt;..."
+        int wm, wn, mt, nt;
+        for (const char* q = L.hooks->force_wino; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
+            for (int k = 0; k < kNumShapes; ++k)
+                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
+                    lds_bytes(kShapes[k], p.kc) <= 160 * 1024) {
+                    s = &kShapes[k];
+                    pinned = true;
+                    per_cu = 1;
+                }
     }
     const bool fused = fuse_xs != nullptr;
     if (fused) {

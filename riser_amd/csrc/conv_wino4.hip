@@ -645,17 +645,16 @@ int launch_conv_wino4(const ConvLayerDev& L, const float* d_x, float* d_y, const
     int per_cu = 1;
     const Shape* s = choose_shape(groups, n16, p.kc, p.nch, num_cu, &single_cost, &per_cu);
     bool pinned = false;                                          // a forced or tuned shape runs as one launch
-    if (const char* force = L.hooks->force_wino4; *force) {       // tuning aid: "layer:wm,wn,mt,nt;..."
-        int l, wm, wn, mt, nt;
-        for (const char* q = force; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr)
-            if (sscanf(q, "%d:%d,%d,%d,%d", &l, &wm, &wn, &mt, &nt) == 5 && l == layer_index)
-                for (int k = 0; k < kNumShapes; ++k)
-                    if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                        lds_bytes(kShapes[k], p.kc) <= 160 * 1024) {
-                        s = &kShapes[k];
-                        pinned = true;
-                        per_cu = 1;
-                    }
+    {   // tuning aid: "layer:wm,wn,mt,nt;..."
+        int wm, wn, mt, nt;
+        for (const char* q = L.hooks->force_wino4; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
+            for (int k = 0; k < kNumShapes; ++k)
+                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
+                    lds_bytes(kShapes[k], p.kc) <= 160 * 1024) {
+                    s = &kShapes[k];
+                    pinned = true;
+                    per_cu = 1;
+                }
     }
     if (const int k = tuned_shape(L, rows64); k >= 0 && conv_wino4_shape_ok(L, k)) {
         s = &kShapes[k];

@@ -1,5 +1,5 @@
-// Sequential conv programs (seqnet.hip), host side: the two weight layouts of the MFMA kernels, one packer over them, and
-// the device buffers the packed matrices are uploaded into.
+// Sequential conv programs (seqnet.hip), host side: the two weight layouts of the MFMA kernels and one packer over them; the
+// packed matrices are uploaded into the device buffers of devbuf.hpp.
 #pragma once
 #include <string.h>
 
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../common.hpp"
+#include "../devbuf.hpp"
 
 namespace rs {
 namespace {
@@ -54,30 +55,6 @@ void pack_conv(std::vector<typename Layout::T>& dst, int NP, int c_out, const Co
         for (int ci = 0; ci < c.c_in; ++ci)
             for (int kk = 0; kk < c.k; ++kk)
                 Layout::put(dst, NP, c.k0 + kk * c.pitch + ci, co, c.w[((size_t)co * c.c_in + ci) * c.k + kk]);
-}
-
-// a device allocation that is freed with its holder (move-only)
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        std::swap(p, o.p);
-        return *this;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    operator T*() const { return p; }
-};
-
-// (at least 16 bytes: the kernels copy weights in 16-byte pieces)
-template <class T>
-hipError_t upload(DevBuf<T>& d, const std::vector<T>& h) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d.p), std::max<size_t>(h.size() * sizeof(T), 16));
-    if (e == hipSuccess) e = hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
 }
 
 // one weight matrix of `elems` elements (its zero padding is part of the layout: the kernels copy all of it to LDS), column pitch

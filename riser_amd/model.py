@@ -634,7 +634,7 @@ def _autotune(self, sig_dev: torch.Tensor, off_dev: torch.Tensor, len_dev: torch
 Model.autotune = _autotune
 
 
-_CONCURRENT_BELOW_SAMPLES = 1800 * 4096          # csrc/api.hip: kConcurrentBelowSamples
+_CONCURRENT_BELOW_SAMPLES = 1800 * 4096          # csrc/api.hip, rs_classify_ensemble: kConcurrentBelowSamples
 
 
 def _ensemble_bytes(models, B: int, lmax: int) -> int:
