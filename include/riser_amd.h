@@ -495,6 +495,52 @@ RS_API int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x /* fp32 [B, ld] *
  * handle is being enqueued. */
 RS_API int rs_crnn_set_mode(rs_crnn* m, int dtype /* rs_dtype */);
 
+/*
+ * Generic ConvNets (added after ABI 2.9; rs_version is unchanged): riser/nets/cnn.py:12-18,43-65 at any `depth` and any odd
+ * `kernels` - n_layers x [depth x (Conv1d(k, stride 1, 'same') + bias + ReLU), MaxPool1d(2, 2)], then the `gap_fc` head
+ * (mean over a read's positions, Linear(c_last -> 2)) + softmax.  A read of L samples has L >> i rows behind i pools; the
+ * shortest read is 2^n_layers samples.  fp32 on the f32-input MFMA (csrc/gconv.hip): one launch for the reads' row counts,
+ * one tiled launch per conv (bias, ReLU and - in a layer's last conv - the max-pool in its epilogue), one for the head.
+ */
+typedef struct rs_gconv_conv {      /* riser/nets/cnn.py:12-18,43-65 */
+    int32_t c_in, c_out, k;         /* chained from c_in = 1; k odd */
+    int32_t reserved;
+    const float* w;                 /* HOST fp32 [c_out, c_in, k] */
+    const float* b;                 /* HOST fp32 [c_out] */
+} rs_gconv_conv;
+typedef struct rs_gconv rs_gconv;
+/* convs: n_layers * depth entries, layer-major (riser/nets/cnn.py:12-18,43-65).  Refused with RS_ERR_ARG before a device is
+ * touched: an even kernel, a conv whose activation slab and weight panel fit no tile shape's LDS, more than 16 layers,
+ * channels that do not chain. */
+RS_API int rs_gconv_create(const rs_gconv_conv* convs, int n_layers, int depth, const float* fc_w /* [2, c_last] */,
+                           const float* fc_b, int device, rs_gconv** out);
+/* riser/nets/cnn.py:12-18,43-65 */
+RS_API int rs_gconv_destroy(rs_gconv* m);
+/* 2^n_layers (riser/nets/cnn.py:12-18,43-65: below it a max_pool has no output); a null handle returns RS_ERR_ARG */
+RS_API int rs_gconv_min_length(const rs_gconv* m);
+/* largest B whose two activation buffers each stay inside the 2 GiB buffer window for reads of pitch ld (riser/nets/cnn.py:12-18,
+ * 43-65 has no such limit); callers split bigger batches.  0 for a null handle or ld below the minimum */
+RS_API int rs_gconv_max_batch(const rs_gconv* m, int ld);
+/* two ping-pong activation buffers + the table of row counts (riser/nets/cnn.py:12-18,43-65); 0 for a null handle, B < 1 or
+ * ld below the minimum */
+RS_API size_t rs_gconv_workspace_bytes(const rs_gconv* m, int B, int ld);
+/* riser/nets/cnn.py:12-18,43-65 on a ragged batch: read b is d_x[b * ld .. b * ld + d_len[b]); what lies behind it in its row
+ * is never read as data.  A read gets the bits it gets alone, whatever the batch, its order or ld.  A d_len beyond ld gives
+ * the bits of d_len = ld; a d_len below the minimum, or negative, gives NaN probabilities for that read and leaves every other
+ * read's bits alone.  ld below the minimum returns RS_ERR_LENGTH.  d_logits may be null. */
+RS_API int rs_gconv_forward_ragged(rs_gconv* m, const float* d_x /* fp32 [B, ld] */, const int32_t* d_len, int B, int ld,
+                                   void* d_ws, size_t ws_bytes, float* d_probs /* [B, 2] */, float* d_logits, void* stream);
+typedef struct rs_gconv_plan {
+    int32_t rows, cols;             /* conv positions x output channels of one workgroup's tile */
+    int32_t kc, n_chunks;           /* input channels per K chunk, chunks */
+    int32_t vec;                    /* 4: K groups of 16 channels; 1: groups of 4 (c_in <= 4) */
+    int32_t lds_bytes;              /* activation slab + weight panel of one chunk */
+    int32_t shape, reserved;        /* index of the tile shape */
+} rs_gconv_plan;
+/* the tile a conv (riser/nets/cnn.py:12-18,43-65) of these sizes takes: a function of (c_in, c_out, k) alone, never of the
+ * batch.  Needs no device.  RS_ERR_ARG for what rs_gconv_create refuses. */
+RS_API int rs_gconv_layer_plan(int c_in, int c_out, int k, rs_gconv_plan* out);
+
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag

@@ -30,6 +30,8 @@ SYMBOLS = (
     "rs_tcn_tile_plan",
     "rs_crnn_create", "rs_crnn_destroy", "rs_crnn_min_length", "rs_crnn_steps", "rs_crnn_workspace_bytes", "rs_crnn_max_batch",
     "rs_crnn_forward_ragged", "rs_crnn_set_mode",
+    "rs_gconv_create", "rs_gconv_destroy", "rs_gconv_min_length", "rs_gconv_max_batch", "rs_gconv_workspace_bytes",
+    "rs_gconv_forward_ragged", "rs_gconv_layer_plan",
 )
 
 
@@ -46,6 +48,11 @@ class SeqLaunch(C.Structure):
 # rs_seq_launch.family
 RS_SEQ_FAMILIES = {1: "stem_pool", 2: "basic_block", 3: "bottleneck", 4: "conv_mfma_lds", 5: "conv_mfma", 6: "conv_scalar",
                    7: "maxpool"}
+
+
+class GConvPlan(C.Structure):
+    """rs_gconv_plan: the tile a generic ConvNet's conv takes (rs_gconv_layer_plan)"""
+    _fields_ = [(n, C.c_int32) for n in ("rows", "cols", "kc", "n_chunks", "vec", "lds_bytes", "shape", "reserved")]
 
 
 class LayerInfo(C.Structure):
@@ -165,6 +172,20 @@ def lib():
     L.rs_crnn_forward_ragged.argtypes = [vp, vp, vp, i32, i32, vp, sz, vp, vp, vp]
     L.rs_crnn_set_mode.restype = i32
     L.rs_crnn_set_mode.argtypes = [vp, i32]
+    L.rs_gconv_create.restype = i32
+    L.rs_gconv_create.argtypes = [vp, i32, i32, vp, vp, i32, C.POINTER(vp)]
+    L.rs_gconv_destroy.restype = i32
+    L.rs_gconv_destroy.argtypes = [vp]
+    L.rs_gconv_min_length.restype = i32
+    L.rs_gconv_min_length.argtypes = [vp]
+    L.rs_gconv_max_batch.restype = i32
+    L.rs_gconv_max_batch.argtypes = [vp, i32]
+    L.rs_gconv_workspace_bytes.restype = sz
+    L.rs_gconv_workspace_bytes.argtypes = [vp, i32, i32]
+    L.rs_gconv_forward_ragged.restype = i32
+    L.rs_gconv_forward_ragged.argtypes = [vp, vp, vp, i32, i32, vp, sz, vp, vp, vp]
+    L.rs_gconv_layer_plan.restype = i32
+    L.rs_gconv_layer_plan.argtypes = [i32, i32, i32, C.POINTER(GConvPlan)]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32

@@ -1,0 +1,173 @@
+"""Generic ConvNets (riser/nets/cnn.py:12-18,43-65 at any `depth` and any odd `kernels`) on the GPU.
+
+The reference builds n_layers x [depth x (Conv1d(k, stride 1, 'same') + ReLU), MaxPool1d(2, 2)] (cnn.py:52-65) and, with the
+`gap_fc` classifier, AdaptiveAvgPool1d(1) + Linear (cnn.py:28-33).  The shipped shape (depth 1, kernel 3) has its own tuned
+path (Model); every other shape runs here: this module folds a reference state dict into a flat conv list (pure numpy, no
+GPU) and drives the device program of csrc/gconv.hip (rs_gconv_*): one tiled launch per conv with bias, ReLU and the layer's
+max-pool in its epilogue, reads of any length in one call.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _native as nv
+
+
+def _np(sd):
+    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
+
+
+def _get(sd, key):
+    if key not in sd:
+        raise ValueError(f"state dict has no {key!r}")
+    return np.ascontiguousarray(sd[key], dtype=np.float32)
+
+
+def build_gconv_program(sd, cnn) -> dict:
+    """dict(convs=[dict(w [co, ci, k], b, k)] (layer-major, n_layers * depth entries), n_layers, depth, fc_w [2, c_last],
+    fc_b [2]) of a reference ConvNet state dict and its `config.cnn`.  Refuses (ValueError) what the device does not run
+    (even kernels, heads other than two-class `gap_fc`) or what does not match the state dict."""
+    n_layers, depth = int(cnn.n_layers), int(getattr(cnn, "depth", 1))
+    channels, kernels = [int(v) for v in cnn.channels], [int(v) for v in cnn.kernels]
+    if n_layers < 1 or depth < 1:
+        raise ValueError("n_layers and depth must be >= 1")
+    if len(channels) < n_layers or len(kernels) < n_layers:
+        raise ValueError(f"channels {channels} / kernels {kernels}: shorter than n_layers {n_layers}")
+    if any(k % 2 == 0 for k in kernels[:n_layers]):
+        raise ValueError("riser_amd: even conv kernels ('same' pads them asymmetrically) are not supported")
+    classifier = getattr(cnn, "classifier", "gap_fc")
+    if classifier != "gap_fc":
+        raise ValueError(f"classifier {classifier!r}: the generic ConvNet family runs the `gap_fc` head only")
+    if int(cnn.n_classes) != 2:
+        raise ValueError("riser_amd supports two-class heads only")
+    sd = _np(sd)
+    convs, c_in = [], 1
+    for i in range(n_layers):
+        for d in range(depth):
+            # nn.Sequential indices of cnn.py:52-65: conv, ReLU, conv, ReLU, ..., MaxPool1d
+            w, b = _get(sd, f"layers.{i}.{2 * d}.weight"), _get(sd, f"layers.{i}.{2 * d}.bias")
+            if w.shape != (channels[i], c_in, kernels[i]) or b.shape != (channels[i],):
+                raise ValueError(f"layers.{i}.{2 * d}: weight {w.shape} / bias {b.shape}, expected ({channels[i]}, {c_in}, "
+                                 f"{kernels[i]}) / ({channels[i]},)")
+            convs.append(dict(w=w, b=b, k=kernels[i]))
+            c_in = channels[i]
+    fw, fb = _get(sd, "classifier.2.weight"), _get(sd, "classifier.2.bias")
+    if fw.shape != (2, c_in) or fb.shape != (2,):
+        raise ValueError(f"classifier.2.weight {fw.shape}: expected (2, {c_in})")
+    return dict(convs=convs, n_layers=n_layers, depth=depth, fc_w=fw, fc_b=fb)
+
+
+def min_length(prog) -> int:
+    """the shortest read the reference can run: every MaxPool1d(2, 2) needs two rows"""
+    return 1 << int(prog["n_layers"])
+
+
+def program_macs(prog, L: int) -> int:
+    """multiply-adds of one read of L samples: every conv on the L >> layer rows it keeps ('same'), head excluded"""
+    total, depth = 0, int(prog["depth"])
+    for i, cv in enumerate(prog["convs"]):
+        co, ci, k = cv["w"].shape
+        total += (int(L) >> (i // depth)) * co * ci * k
+    return int(total)
+
+
+class _Conv(C.Structure):
+    _fields_ = [("c_in", C.c_int32), ("c_out", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32),
+                ("w", C.c_void_p), ("b", C.c_void_p)]
+
+
+def layer_plan(c_in: int, c_out: int, k: int) -> dict:
+    """the tile a conv of these sizes takes (rs_gconv_layer_plan): rows x cols of a workgroup, the K chunk, its LDS; a
+    function of the conv alone, never of the batch.  Needs no GPU."""
+    p = nv.GConvPlan()
+    nv.check(nv.lib().rs_gconv_layer_plan(int(c_in), int(c_out), int(k), C.byref(p)), "rs_gconv_layer_plan")
+    return {n: int(getattr(p, n)) for n, _ in nv.GConvPlan._fields_ if n != "reserved"}
+
+
+class GConvNet:
+    """A generic ConvNet on the device (rs_gconv_*): the surface Model drives for SeqNet - forward, forward_ragged,
+    max_batch.  fp32 on the f32-input MFMA only."""
+
+    ragged_ok = True
+
+    def __init__(self, prog, device, dtype: str = "f32"):
+        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32"}.get(dtype)
+        if self.dtype is None:
+            raise ValueError(f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic fp32 "
+                             "conv program only")
+        nv.require_gpu()
+        d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
+        self._keep = prog
+        convs = (_Conv * len(prog["convs"]))()
+        for i, cv in enumerate(prog["convs"]):
+            co, ci, k = cv["w"].shape
+            convs[i] = _Conv(ci, co, k, 0, cv["w"].ctypes.data, cv["b"].ctypes.data)
+        h = C.c_void_p()
+        nv.check(nv.lib().rs_gconv_create(convs, int(prog["n_layers"]), int(prog["depth"]), prog["fc_w"].ctypes.data,
+                                          prog["fc_b"].ctypes.data, self.device.index, C.byref(h)), "rs_gconv_create")
+        self._h = h
+        self._ws = None
+
+    @property
+    def min_length(self) -> int:
+        return int(nv.lib().rs_gconv_min_length(self._h))
+
+    def layer_plans(self):
+        """layer_plan of every conv, in launch order"""
+        return [layer_plan(cv["w"].shape[1], cv["w"].shape[0], cv["w"].shape[2]) for cv in self._keep["convs"]]
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            nv.lib().rs_gconv_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def max_batch(self, L: int) -> int:
+        """largest batch of reads of (pitch) L samples one call can address: both activation buffers inside the 2 GiB window
+        (rs_gconv_max_batch); forward_ragged splits bigger batches"""
+        return max(1, int(nv.lib().rs_gconv_max_batch(self._h, int(L))))
+
+    def forward(self, x: torch.Tensor, return_logits: bool = False):
+        """x: fp32 device tensor [B, L] (one common length) -> fp32 [B, 2] on the device."""
+        B, L = x.shape
+        lens = torch.full((B,), L, dtype=torch.int32, device=self.device)
+        return self.forward_ragged(x, lens, return_logits)
+
+    def forward_ragged(self, x: torch.Tensor, lens_dev: torch.Tensor, return_logits: bool = False, out: torch.Tensor = None):
+        """x: fp32 device tensor [B, ld], read b = x[b, :lens_dev[b]] (int32 on the device) -> fp32 [B, 2] on the device;
+        every read's result is that of forward() on it alone, bit for bit."""
+        B, ld = x.shape
+        if not x.is_contiguous():                   # the device reads row b at x + b * ld
+            raise ValueError("x must be contiguous: its row pitch is its second dimension")
+        lib = nv.lib()
+        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
+        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
+        mb = self.max_batch(ld)
+        if B > mb:                                  # reads are independent: equal parts, each inside the buffer window
+            parts = -(-B // mb)
+            step = -(-B // parts)
+            for s0 in range(0, B, step):
+                s1 = min(B, s0 + step)
+                r = self.forward_ragged(x[s0:s1], lens_dev[s0:s1], return_logits, out=probs[s0:s1])
+                if return_logits:
+                    logits[s0:s1] = r[1]
+            return (probs, logits) if return_logits else probs
+        need = lib.rs_gconv_workspace_bytes(self._h, B, ld)
+        if need == 0:
+            raise ValueError(f"no workspace for {B} reads of {ld} samples (the network minimum is {self.min_length})")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        nv.check(lib.rs_gconv_forward_ragged(self._h, x.data_ptr(), lens_dev.data_ptr(), B, ld, self._ws.data_ptr(),
+                                             self._ws.numel(), probs.data_ptr(), logits.data_ptr() if return_logits else None,
+                                             torch.cuda.current_stream(self.device).cuda_stream), "rs_gconv_forward_ragged")
+        return (probs, logits) if return_logits else probs

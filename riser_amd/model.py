@@ -151,16 +151,24 @@ class Model:
         self._seq = None
         self.model = self            # the reference exposes the nn.Module here; kept as an alias
         if int(getattr(cnn, "depth", 1)) != 1 or any(int(k) != 3 for k in list(cnn.kernels)[: self.n_layers]):
-            # outside the shipped class (depth > 1 or kernels other than 3, riser/nets/cnn.py:17,52-65): the generic
-            # conv / max-pool program of csrc/seqnet.hip (f32-input MFMA, reads grouped by length)
-            from .resnet import SeqNet, build_convnet_program
+            # outside the shipped class (depth > 1 or kernels other than 3, riser/nets/cnn.py:17,52-65).  With the `gap_fc`
+            # head: the generic ConvNet family of csrc/gconv.hip (tiled conv + ReLU + pool launches, reads of any length in
+            # one call).  RS_GCONV=0 or RS_SEQ_SCALAR=1 in the environment now, and the `gap` head, keep the conv / max-pool
+            # program of csrc/seqnet.hip (reads grouped by length)
             if int(cnn.n_classes) != 2:
                 raise ValueError("riser_amd supports two-class heads only")
-            self._seq = SeqNet(*build_convnet_program(sd, cnn), device=self.device)
             self._h = None
+            if any(int(k) % 2 == 0 for k in list(cnn.kernels)[: self.n_layers]):
+                raise ValueError("riser_amd: even conv kernels ('same' pads them asymmetrically) are not supported")
             if dtype not in ("f32w", "f32"):
                 raise ValueError(f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic fp32 "
                                  "conv program only")
+            if self.classifier == "gap_fc" and os.environ.get("RS_GCONV", "1") != "0" and "RS_SEQ_SCALAR" not in os.environ:
+                from .gconv import GConvNet, build_gconv_program
+                self._seq = GConvNet(build_gconv_program(sd, cnn), device=self.device)
+            else:
+                from .resnet import SeqNet, build_convnet_program
+                self._seq = SeqNet(*build_convnet_program(sd, cnn), device=self.device)
             self.dtype = "f32"
             self._ws = Workspace(self.device)
             return

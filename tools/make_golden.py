@@ -10,7 +10,7 @@ own code returned for them.
 
 Reference entry points exercised:
   F1  SignalProcessor.mad_normalise          riser/preprocess.py:108-147  (F1b: float32 / float64 inputs)
-  F2  Model.classify / ConvNet.forward        riser/model.py:22-28, riser/nets/cnn.py:43-65  (F2b: depth > 1 / odd kernels; F2c: `gap` head; F2d: `fc` head)
+  F2  Model.classify / ConvNet.forward        riser/model.py:22-28, riser/nets/cnn.py:43-65  (F2b: depth > 1 / odd kernels; F2c: `gap` head; F2d: `fc` head; F2e: edge configs of the generic family)
   F3  SequencerControl.target                 riser/control.py:11-124 (fake client)
   F4  SignalProcessor.get_polyA_end           riser/preprocess.py:42-79
   F5  ResNet.forward                          riser/nets/resnet.py  (F5b: edge configs of the launch-form sweep)
@@ -270,6 +270,39 @@ def f2b_convnet_variants():
             out[f"{name}.sd.{k}"] = v
         print("F2b:", name, np.stack(probs)[:, 1])
     np.savez_compressed(os.path.join(OUT, "convnet_variants.npz"), **out)
+
+
+# --------------------------------------------------------------------------------------
+def f2e_gconv_edges():
+    """F2b at the edges of the generic family's shape arithmetic, on six configs of tests/gconv_ref.py (taken from there
+    with their seeds, so the two cannot drift apart): kernels 1, 9 and 19, a 5-3-7-3 mix, depth 1 - 3, 17 / 33 / 65
+    channels.  Logits of three synth reads per length from the reference's own ConvNet on the CPU; prints the largest gap
+    to the float64 forward of tests/gconv_ref.py."""
+    from nets.cnn import ConvNet
+    from riser_amd import gconv as G
+    from tests import gconv_ref as R
+    out, worst = {}, 0.0
+    proc = SignalProcessor(Kit.create_from_version("RNA004"))
+    for name in R.GOLDEN_EDGES:
+        cfg, seed = R.CONFIGS[name], R.SEED[name]
+        cnn = R.cnn_config(cfg)
+        net = ConvNet(cnn)
+        sd = R.make_state_dict(cfg, seed)
+        net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+        net.eval()
+        prog = G.build_gconv_program(sd, cnn)
+        lo = G.min_length(prog)
+        lens = [lo if L == "min" else lo + 1 if L == "min+1" else int(L) for L in R.GOLDEN_LENGTHS]
+        for L in lens:
+            sigs = synth.make_signals(SIG_SEED, 3, L, first_read=60)
+            x = np.stack([proc.mad_normalise(s.copy()) for s in sigs]).astype(np.float32)
+            with torch.no_grad():
+                logits = net(torch.from_numpy(x)).numpy()
+            out[f"{name}.L{L}.logits"] = logits
+            worst = max(worst, R.gap(logits, R.forward(prog, x, [L] * 3)))
+        out[f"{name}.cfg"] = np.array(json.dumps(dict(cfg, lengths=lens, seed=seed)))
+        print("F2e:", name, "min", lo, "float64 gap so far %.2e" % worst)
+    np.savez_compressed(os.path.join(OUT, "gconv_edges.npz"), **out)
 
 
 # --------------------------------------------------------------------------------------
@@ -709,6 +742,8 @@ if __name__ == "__main__":
         f2c_gap_head()
     if "f2d" in which or "f2" in which:
         f2d_fc_head()
+    if "f2e" in which:
+        f2e_gconv_edges()
     if "f3" in which:
         f3_control()
     if "f5" in which:
