@@ -545,8 +545,11 @@ RS_API int rs_gconv_layer_plan(int c_in, int c_out, int k, rs_gconv_plan* out);
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag
  * on the model; the launch entry points still return RS_OK.  rs_model_saturated waits for `stream` and returns 1 if any call
- * since the last reset overflowed, 0 if none did (always 0 for the fp32 and bf16 modes), a negative rs_status on error; `reset`
- * != 0 clears the flag behind the read.  (ABI 2.5) */
+ * since the last reset overflowed, 0 if none did (always 0 for the fp32 and bf16 modes, before any device call), a negative
+ * rs_status on error; `reset` != 0 clears the flag.  The read and the clear are ONE atomic exchange in a single-thread kernel
+ * on `stream` (its result reaches the host through a pinned word the model owns): an overflow raised by a kernel on ANY
+ * stream is either seen by this call or left for the next one - it is never dropped between a read and a separate clear.
+ * One call at a time per model (the pinned word is the model's), as for the launch entry points.  (ABI 2.5) */
 RS_API int rs_model_saturated(rs_model* m, int reset, void* stream);
 
 /*

@@ -20,6 +20,11 @@ batch 1, a device sync per probability (riser/control.py:31-93,152) - whereas th
   6. sends the reject / finish calls, THEN writes the CSV rows of the batch (the reference writes each row before the
      calls; the file's content is the same, the pore learns its decision earlier).
 
+Half-precision models (f16 / f16x3 / f16xf8) can overflow where the reference's fp32 call cannot; `on_overflow` says what a
+batch in which one did sends to the sequencer: "warn" (the decisions as computed, and a warning in the log), "reclassify" (the
+batch classified again with the overflowed models replaced by their bf16x3 twins, before anything is sent) or "try_again" (no
+accept / reject of that batch leaves the process: DESIGN.md 7).
+
 Host work per batch is numpy over arrays of the batch's reads.  What is left per read in Python is what the client's own
 interface forces - one `get_raw_signal` call and one `read.id` per read; a client that declares `raw_data_dtype = np.int16`
 (its get_raw_signal is np.frombuffer(read.raw_data, int16), as riser/client.py:46-47 is) has its reads walked by the C loops
@@ -59,6 +64,12 @@ _CSV_COLUMNS = ("batch_start", "read_id", "channel", "sig_length", "models", "pr
                 "decision")
 _CACHE_LIMIT = 1000                  # poly(A) cache entries before it is dropped (riser/control.py:96-97)
 _MINION_CHANNELS = 512               # riser/client.py:11
+ON_OVERFLOW = ("warn", "reclassify", "try_again")
+_WARN_OVERFLOW = {
+    "reclassify": ('RISER: a half-precision model overflowed on this run\'s data; the affected batches are classified again in '
+                   'bf16x3 before any decision is sent. Load the model as bf16x3 or f32w to avoid the extra pass.'),
+    "try_again": ('RISER: a half-precision model overflowed on this run\'s data; no accept or reject is sent for the affected '
+                  'batches (their reads are assessed again with more signal). Load the model as bf16x3 or f32w.')}
 PHASES = ("client_reads", "stage_upload", "polya_sync", "gate_launch", "device_wait", "client_calls", "csv")
 
 
@@ -501,11 +512,34 @@ class _Assessed:
                     self.decision.tolist())]
 
 
+def withhold_decisions(decisions, lengths, max_len: int) -> np.ndarray:
+    """on_overflow="try_again": the decisions of a batch whose probabilities cannot be trusted -> what is sent instead.  An
+    `accept` or `reject` of a read still below `max_len` samples becomes `try_again` (the read comes back with more signal); at
+    `max_len` it becomes `no_decision` (the read is finished, as the reference finishes a read at maximum length, and no unblock
+    is sent: riser/control.py:79-82).  `try_again` and `no_decision` stay.  Returns a new uint8 array."""
+    dec = np.array(decisions, dtype=np.uint8, copy=True)
+    decided = (dec == nv.RS_ACCEPT) | (dec == nv.RS_REJECT)
+    at_max = np.asarray(lengths) >= int(max_len)
+    dec[decided & at_max] = nv.RS_NO_DECISION
+    dec[decided & ~at_max] = nv.RS_TRY_AGAIN
+    return dec
+
+
 class SequencerControl:
-    def __init__(self, client, models, processor, logger, out_file, signal_cache: bool = True):
-        """signal_cache=False uploads every read whole with every batch (no device-resident signals)."""
+    def __init__(self, client, models, processor, logger, out_file, signal_cache: bool = True, on_overflow: str = "warn"):
+        """signal_cache=False uploads every read whole with every batch (no device-resident signals).
+        on_overflow: what a batch in which a half-precision model overflowed sends - "warn" (default: its decisions as
+        computed, one log warning per batch), "reclassify" (the batch again, overflowed models replaced by their bf16x3
+        twins) or "try_again" (its accepts and rejects withheld: withhold_decisions)."""
+        if on_overflow not in ON_OVERFLOW:
+            raise ValueError(f"on_overflow must be one of {ON_OVERFLOW}, got {on_overflow!r}")
         self.client, self.models, self.proc, self.logger = client, models, processor, logger
+        self.on_overflow = on_overflow
         self.saturated_batches = 0          # batches in which a half-precision model overflowed (warned about, each)
+        self.reclassified_batches = 0       # ... of them, batches classified again with the twins ("reclassify")
+        self.withheld_batches = 0           # ... batches whose accepts / rejects were withheld ("try_again")
+        self._twins = {}                    # "reclassify": index in models -> the model's bf16x3 twin (created in reserve())
+        self._overflow_notified = False     # the operator's warning goes out once per run
         self.out_filename = out_file
         # host wall time of the most recent assessed batches (seconds): bounded, a run lasts tens of hours.
         # batch_latencies: get_read_batch() -> reject / finish calls sent (what the pore waits for);
@@ -529,15 +563,42 @@ class SequencerControl:
         device rows, the pinned staging buffers and the result buffers - so that no batch of the run pays for a device
         allocation or a page-locking system call (a growing workspace is a multi-GB hipMalloc + hipFree inside a 1 s
         window)."""
-        from .model import reserve_ensemble
+        from .model import reserve_ensemble, reserve_ensemble_sets
         reads = int(reads)
         # the largest call of a run is one slice (assess_batch), not the flow cell's channel count
-        reserve_ensemble(self.models, min(reads, self.SLICE_READS * 3 // 2 + 1), self.proc.get_max_length())
+        call_reads, max_len = min(reads, self.SLICE_READS * 3 // 2 + 1), self.proc.get_max_length()
+        reserve_ensemble(self.models, call_reads, max_len)
+        if self.on_overflow == "reclassify":
+            # the twins exist, with their workspace, BEFORE the run: a saturated batch pays for a second pass, not for a
+            # model upload and a device allocation inside its 1 s window
+            self._ensure_twins()
+            if self._twins:
+                reserve_ensemble_sets([self.models, self._with_twins(self._twins)], call_reads, max_len)
         # a first batch carries every read whole: typically <= 6 s of signal per pore
         self._store.reserve(reads, min(reads * 24576, 1 << 29))
         self._pinned.reset(96 * reads + (1 << 12))
         self._result_buffers(reads)
         self._reserved_for = max(self._reserved_for, reads)
+
+    @property
+    def twins(self) -> tuple:
+        """per model: its fp32-range twin (on_overflow="reclassify", after reserve() or the first batch) or None"""
+        return tuple(self._twins.get(k) for k in range(len(self.models)))
+
+    def _ensure_twins(self):
+        for k, m in enumerate(self.models):
+            if k not in self._twins and getattr(m, "is_half", False):
+                self._twins[k] = m.fp32_range_twin()
+
+    def _with_twins(self, which) -> list:
+        """the models, those of the indices `which` replaced by their twins"""
+        return [self._twins[k] if k in which else m for k, m in enumerate(self.models)]
+
+    def close(self):
+        """release the twins (the models themselves belong to the caller)"""
+        twins, self._twins = self._twins, {}
+        for tw in twins.values():
+            tw.close()
 
     def _result_buffers(self, n: int):
         n_models = len(self.models)
@@ -615,6 +676,8 @@ class SequencerControl:
         self._result_buffers(B)
         flat_p, flat_d = self._res_probs.dev.view(-1), self._res_dec.dev
         parts, n_total = [], 0
+        # "reclassify": the device offsets / lengths of every part stay alive until the batch is done (a second pass reads them)
+        dev_parts = [] if self.on_overflow == "reclassify" else None
         pa_host = self._polya_host
         while len(self._pa_events) < n_slices:
             self._pa_events.append(torch.cuda.Event())
@@ -691,6 +754,8 @@ class SequencerControl:
             classify_raw_ensemble(self.models, store.buf, off_d, len_d, lens_a, out=probs_d, decision=dec_d, max_len=max_len,
                                   threshold=threshold, mode=_MODE[mode])
             parts.append((lo + sel, lens_a, n_total, n_sel))
+            if dev_parts is not None:
+                dev_parts.append((off_d, len_d))
             n_total += n_sel
             t, dt = self._tick(t, 3)
             ph[3] += dt
@@ -732,17 +797,42 @@ class SequencerControl:
             side.synchronize()
         # half-precision models: an activation beyond 65504 leaves the conversion as +inf and the read's probabilities are
         # wrong - the reference's fp32 call (riser/model.py:22-28) cannot do that, so the loop says so (csrc: rs_model_saturated)
-        for m in self.models:
-            if getattr(m, "dtype", None) in getattr(m, "HALF_MODES", ()) and m.saturated(reset=True):
+        overflowed = set()
+        for k, m in enumerate(self.models):
+            if getattr(m, "is_half", False) and m.saturated(reset=True):
+                overflowed.add(k)
                 self.saturated_batches += 1
                 self.logger.warning(f"target {m.target!r} ({m.dtype}): an activation overflowed half precision in this batch of "
                                     f"{n_total} reads - their probabilities are unreliable; load the model as 'bf16x3' or 'f32w'")
+        if overflowed and self.on_overflow != "warn":
+            if not self._overflow_notified:                  # the operator watches the client's channel, not the log
+                self._overflow_notified = True
+                self.client.send_warning(_WARN_OVERFLOW[self.on_overflow])
+            if self.on_overflow == "reclassify":
+                # the same reads through the same entry point into the same slots of the result buffers, part by part, the
+                # overflowed models replaced by their twins (the others keep their arithmetic); both streams are idle here
+                self._ensure_twins()
+                again = self._with_twins(overflowed)
+                for (_, lens_a, at, n), (off_d, len_d) in zip(parts, dev_parts):
+                    classify_raw_ensemble(again, store.buf, off_d, len_d, lens_a,
+                                          out=flat_p[n_models * 2 * at: n_models * 2 * (at + n)].view(n_models, n, 2),
+                                          decision=flat_d[at: at + n], max_len=max_len, threshold=threshold, mode=_MODE[mode])
+                probs_h.copy_(flat_p[: n_models * 2 * n_total], non_blocking=True)
+                dec_h.copy_(flat_d[:n_total], non_blocking=True)
+                caller.synchronize()
+                self.reclassified_batches += 1
         pn, dn = probs_h.numpy(), dec_h.numpy()
         p_on = np.empty((n_total, n_models), dtype=np.float64)                              # [read][model]
         for _, _, at, n in parts:
             p_on[at: at + n] = pn[n_models * 2 * at: n_models * 2 * (at + n)].reshape(n_models, n, 2)[:, :, 1].T
         sel_all = np.concatenate([p[0] for p in parts])
-        res = _Assessed(reads, sel_all, channels[sel_all], np.concatenate([p[1] for p in parts]), p_on, dn.copy())
+        n_samples = np.concatenate([p[1] for p in parts])
+        if overflowed and self.on_overflow == "try_again":
+            decision = withhold_decisions(dn, n_samples, max_len)       # the probabilities stay as computed (the CSV shows them)
+            self.withheld_batches += 1
+        else:
+            decision = dn.copy()
+        res = _Assessed(reads, sel_all, channels[sel_all], n_samples, p_on, decision)
         t, ph[4] = self._tick(t, 4)
         return res
 
@@ -765,6 +855,7 @@ class SequencerControl:
         if mode not in _MODE:
             raise ValueError(f"mode must be 'enrich' or 'deplete', got {mode!r}")
         client = self.client
+        self._overflow_notified = False
         client.send_warning(_WARN_START)
         with open(f"{self.out_filename}.csv", "a") as sink:
             sink.write(",".join(_CSV_COLUMNS) + "\n")
@@ -849,6 +940,7 @@ class SequencerControl:
         self.logger.info("Live read stream started.")
 
     def finish(self):
+        self.close()
         self.client.reset()
         self.logger.info("Client reset and live read stream ended.")
 

@@ -79,6 +79,15 @@ const Hooks& default_hooks() {
     return h;
 }
 
+namespace {
+// rs_model_saturated: one thread moves the model's sticky overflow word to a pinned host word; with `reset` the read and the
+// clear are one atomic exchange, so nothing raised between them can be lost
+__global__ void read_flag_kernel(unsigned* __restrict__ flag, unsigned* __restrict__ host_word, int reset) {
+    const unsigned old = reset ? atomicExch(flag, 0u) : __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(host_word, old, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+}  // namespace
+
 }  // namespace rs
 
 using namespace rs;
@@ -502,11 +511,12 @@ int rs_model_saturated(rs_model* m, int reset, void* stream) {
     DeviceGuard guard(m->device);
     RS_HIP(guard.err);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned v = 0;
-    RS_HIP(hipMemcpyAsync(&v, m->d_sat, sizeof(v), hipMemcpyDeviceToHost, st));
-    if (reset) RS_HIP(hipMemsetAsync(m->d_sat, 0, sizeof(v), st));
+    // ONE atomic operation reads the flag and (with `reset`) clears it: an epilogue of a kernel on another stream that raises
+    // the flag lands before the exchange (this call returns 1) or behind it (the flag stays set for the next call)
+    hipLaunchKernelGGL(read_flag_kernel, dim3(1), dim3(1), 0, st, m->d_sat.p, m->h_sat.p, reset ? 1 : 0);
+    RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(st));
-    return v ? 1 : 0;
+    return *static_cast<volatile unsigned*>(m->h_sat.p) ? 1 : 0;
 }
 
 int rs_debug_capture_layer(rs_model* m, int layer, void* d_dst, size_t bytes) {

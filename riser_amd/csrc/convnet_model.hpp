@@ -42,6 +42,7 @@ struct rs_model {
     rs::DevBuf<float> fc_w1p, fc_b1, fc_w2, fc_b2;
     rs::DevBuf<float> d_zero;             // 256 zero bytes: target of masked-off staging loads
     rs::DevBuf<unsigned> d_sat;           // half-precision modes: sticky word, non-zero once an activation overflowed f16 (rs_model_saturated)
+    rs::PinnedWord h_sat;                 // ... and the pinned host word rs_model_saturated's kernel stores the flag's value into
     int num_cu = 256;
     int last_bm[rs::kMaxLayers] = {0};
     int last_bn[rs::kMaxLayers] = {0};
@@ -244,8 +245,14 @@ int model_build(rs_model* m, int n_layers, const int32_t* channels, const float*
         m->cp[i] = row_pitch(dtype, channels[i], f8[i] && f8[i + 1]);
     }
     int rc = RS_OK;
-    if (is_f16_family(dtype)) rc = upload_owned(m->d_sat, std::vector<unsigned>(1, 0u));
-    rc = upload_owned(m->d_w0, pack_layer0(m->cp[0], channels[0], conv_w[0], conv_b[0]));
+    if (is_f16_family(dtype)) {
+        rc = upload_owned(m->d_sat, std::vector<unsigned>(1, 0u));
+        if (rc == RS_OK) {
+            const hipError_t e = m->h_sat.alloc();
+            if (e != hipSuccess) rc = hip_fail(e, "hipHostMalloc(&h_sat, sizeof(unsigned))");
+        }
+    }
+    if (rc == RS_OK) rc = upload_owned(m->d_w0, pack_layer0(m->cp[0], channels[0], conv_w[0], conv_b[0]));
     for (int i = 1; i < n_layers && rc == RS_OK; ++i) {
         ConvLayerDev& L = m->layers[i];
         L.hooks = &m->hooks;

@@ -24,6 +24,26 @@ struct DevBuf {
     operator T*() const { return p; }
 };
 
+// one pinned host word a kernel can store into, freed with its holder (move-only)
+struct PinnedWord {
+    unsigned* p = nullptr;
+    PinnedWord() = default;
+    PinnedWord(PinnedWord&& o) noexcept : p(o.p) { o.p = nullptr; }
+    PinnedWord& operator=(PinnedWord&& o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~PinnedWord() {
+        if (p) (void)hipHostFree(p);
+    }
+    hipError_t alloc() {
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(unsigned), hipHostMallocDefault);
+        if (e == hipSuccess) *p = 0u;
+        return e;
+    }
+    operator unsigned*() const { return p; }
+};
+
 // (at least 16 bytes: the kernels copy weights in 16-byte pieces, and an empty vector still gets an allocation)
 template <class T>
 hipError_t upload(DevBuf<T>& d, const std::vector<T>& h) {

@@ -3,6 +3,7 @@
     python -m riser_amd.launch --gpus N --channels C --kit RNA004 --mode enrich --out run \\
         [--client pkg.module:factory] [--model-dir model --targets mRNA,mtRNA | --model target=state.pth ...]
         [--dtype f32w] [--duration-h 48] [--threshold 0.9] [--on-rank-failure abort|restart] [--max-restarts 2]
+        [--on-overflow warn|reclassify|try_again]
         [--replay-script tests/golden/control.json | --replay-synthetic BATCHES] [--seeds 1,2,3] [--share-gpus] [--stub]
 
 The reference drives ONE flow cell from one process: `ReadUntilClient.run(first_channel=1, last_channel=512)` and one
@@ -93,6 +94,10 @@ def parse_args(argv=None):
     ap.add_argument("--replay-synthetic", type=int, default=0, metavar="BATCHES")
     ap.add_argument("--share-gpus", action="store_true", help="allow more ranks than visible devices: rank r runs on device r mod devices (2-3 channel ranges per GPU fill the device while each rank's host code runs; also: rehearsal on one GPU)")
     ap.add_argument("--no-signal-cache", action="store_true")
+    ap.add_argument("--on-overflow", default="warn", choices=["warn", "reclassify", "try_again"],
+                    help="a batch in which a half-precision model (f16 / f16x3 / f16xf8) overflowed: send its decisions with a log "
+                         "warning (warn), classify it again in bf16x3 first (reclassify), or withhold its accepts / rejects "
+                         "(try_again); every rank's SequencerControl takes it")
     ap.add_argument("--stub", action="store_true", help="no GPU: every received read becomes a 'try_again' CSV row")
     return ap.parse_args(argv)
 
@@ -334,7 +339,8 @@ def run_rank(args) -> int:
             models = [Model(synth.make_state_dict(int(s)), synth.Config(), logger, names[k % 3], dtype=args.dtype, device=device)
                       for k, s in enumerate(args.seeds.split(","))]
         proc = SignalProcessor(Kit.create_from_version(args.kit), device=device)
-        ctl = SequencerControl(client, models, proc, logger, out, signal_cache=not args.no_signal_cache)
+        ctl = SequencerControl(client, models, proc, logger, out, signal_cache=not args.no_signal_cache,
+                               on_overflow=args.on_overflow)
         ctl.reserve(max(512, last - first + 1))
     t0 = time.perf_counter()
     ctl.start()
@@ -352,7 +358,10 @@ def run_rank(args) -> int:
                "rejected_lists": getattr(client, "rejected", None) if args.replay_script else None,
                "finished_lists": getattr(client, "finished", None) if args.replay_script else None,
                "p50_ms": round(lat[len(lat) // 2] * 1e3, 3) if lat else None,
-               "max_ms": round(lat[-1] * 1e3, 3) if lat else None, "latency_samples": len(lat)}
+               "max_ms": round(lat[-1] * 1e3, 3) if lat else None, "latency_samples": len(lat),
+               "on_overflow": args.on_overflow, "saturated_batches": int(getattr(ctl, "saturated_batches", 0)),
+               "reclassified_batches": int(getattr(ctl, "reclassified_batches", 0)),
+               "withheld_batches": int(getattr(ctl, "withheld_batches", 0))}
     print(json.dumps(summary), flush=True)
     return 0
 

@@ -19,6 +19,16 @@ _DTYPES = {"f32": nv.RS_F32, "fp32": nv.RS_F32, "float32": nv.RS_F32,
            "bf16": nv.RS_BF16, "bfloat16": nv.RS_BF16, "f16": nv.RS_F16, "fp16": nv.RS_F16,
            "float16": nv.RS_F16, "f32w": nv.RS_F32W, "f32_winograd": nv.RS_F32W,
            "bf16x3": nv.RS_BF16X3, "f16x3": nv.RS_F16X3, "f16xf8": nv.RS_F16XF8}
+# the library dtypes that store activations as IEEE half, and the canonical name of every library dtype ("fp16" -> "f16")
+_HALF_LIB_DTYPES = (nv.RS_F16, nv.RS_F16X3, nv.RS_F16XF8)
+_CANONICAL = {nv.RS_F32: "f32", nv.RS_BF16: "bf16", nv.RS_F16: "f16", nv.RS_F32W: "f32w", nv.RS_BF16X3: "bf16x3",
+              nv.RS_F16X3: "f16x3", nv.RS_F16XF8: "f16xf8"}
+
+
+def is_half_dtype(dtype: str) -> bool:
+    """True when `dtype` - a canonical name or an alias ("fp16", "float16") - selects a library mode that stores activations
+    as IEEE half (RS_F16 / RS_F16X3 / RS_F16XF8): decided by the library dtype the name maps to, not by its spelling"""
+    return _DTYPES.get(dtype) in _HALF_LIB_DTYPES
 
 
 def _stream_ptr(device) -> int:
@@ -146,7 +156,8 @@ class Model:
             sd["classifier.2.weight"] = np.zeros((int(cnn.n_classes), c_last), dtype=np.float32)
             sd["classifier.2.bias"] = np.zeros(int(cnn.n_classes), dtype=np.float32)
         self.min_length = 1 << self.n_layers
-        self.dtype = dtype
+        self.dtype = dtype                     # the caller's spelling; _canonical is what tables are keyed by
+        self._canonical = _CANONICAL.get(_DTYPES.get(dtype), dtype)
         self._keep = []
         self._seq = None
         self.model = self            # the reference exposes the nn.Module here; kept as an alias
@@ -195,6 +206,9 @@ class Model:
                                    fc_b.ctypes.data, _DTYPES[dtype], self.device.index, C.byref(h)),
                  "rs_model_create")
         self._h = h
+        self._lib_dtype = _DTYPES[dtype]
+        # a half-precision model keeps the host fp32 arrays it was built from (a few MB): fp32_range_twin() needs no file
+        self._twin_source = (sd, config) if self.is_half else None
         self._ws = Workspace(self.device)
         if fc is not None:
             w1, b1, w2, b2 = fc
@@ -202,7 +216,7 @@ class Model:
             nv.check(L.rs_model_set_fc_classifier(h, positions, int(w1.shape[0]), w1.ctypes.data, b1.ctypes.data,
                                                   w2.ctypes.data, b2.ctypes.data), "rs_model_set_fc_classifier")
             self._fc_positions, self._fc_hidden = positions, int(w1.shape[0])
-        if dtype in self.HALF_MODES and range_check and os.environ.get("RS_RANGE_CHECK", "1") != "0":
+        if self.is_half and range_check and os.environ.get("RS_RANGE_CHECK", "1") != "0":
             try:
                 self._half_range_check()
             except Exception:
@@ -210,6 +224,24 @@ class Model:
                 raise
 
     # ---- half precision's range ----------------------------------------------------------
+    @property
+    def is_half(self) -> bool:
+        """this model runs a library mode that stores activations as IEEE half (a range of 65504) and carries the overflow
+        flag: the shipped ConvNet family in f16 / f16x3 / f16xf8, under any spelling of those names.  False for every other
+        mode, the generic programs and the CNN-RNN's f16x3 (bounded operands, no flag)."""
+        return getattr(self, "_lib_dtype", None) in _HALF_LIB_DTYPES
+
+    def fp32_range_twin(self) -> "Model":
+        """A `bf16x3` Model of the same weights, target and device: fp32's exponent range (its saturated() is always False),
+        within 1e-3 of the reference, at the speed of the half modes - what the control loop classifies a batch with again
+        when this model overflowed (SequencerControl(on_overflow="reclassify")).  Built from the host arrays this model
+        kept; the caller owns and closes it."""
+        if not self.is_half or self._twin_source is None:
+            raise ValueError(f"fp32_range_twin: dtype {self.dtype!r} of target {self.target!r} is not a half-precision mode "
+                             "of the shipped ConvNet family - it cannot overflow and has no twin")
+        sd, config = self._twin_source
+        return Model(sd, config, self.logger, self.target, dtype="bf16x3", device=self.device)
+
     def half_activation_maxima(self, signals=None) -> list:
         """largest activation (the hi half) of every conv layer i >= 1 of THIS half-precision model on raw int16 `signals`
         (default: 16 synthetic reads of riser_amd.synth; MAD-normalised input is confined to ~[-3.5, 3.5] whatever the
@@ -256,7 +288,7 @@ class Model:
         """True if a half-precision conversion overflowed (an activation beyond 65504) in any call on this model since the
         flag was last reset; waits for the caller's stream.  Always False for the fp32 / bf16 modes and the generic conv
         programs (fp32's exponent range)."""
-        if self._h is None or self.dtype not in self.HALF_MODES:
+        if self._h is None or not self.is_half:
             return False
         rc = nv.lib().rs_model_saturated(self._h, 1 if reset else 0, _stream_ptr(self.device))
         if rc < 0:
@@ -446,7 +478,7 @@ class Model:
         hard = self.max_batch(lmax)
         cap = hard
         if self._seq is None:
-            cap = min(hard, max(512, self._CALL_SAMPLES.get(self.dtype, 2048 << 14) // ((int(lmax) // 1024 + 1) * 1024)))
+            cap = min(hard, max(512, self._CALL_SAMPLES.get(getattr(self, "_canonical", self.dtype), 2048 << 14) // ((int(lmax) // 1024 + 1) * 1024)))
         if B <= cap or B <= min(hard, cap + cap // 4):          # the cache-friendly size is a preference: no sliver calls
             return B
         n = -(-B // cap)
@@ -505,7 +537,7 @@ class Model:
         ln.copy_(slot["len"], non_blocking=True)
         slot["free"].record()
         out = self.forward_batch(x, lens, lens_dev=ln)[0]
-        if self.dtype in self.HALF_MODES:          # the reference's fp32 call cannot overflow: say so when this one did
+        if self.is_half:                           # the reference's fp32 call cannot overflow: say so when this one did
             self.warn_if_saturated("classify()")
         return out
 
@@ -667,6 +699,22 @@ def reserve_ensemble(models, B: int, lmax: int):
         return
     B = max(1, min(m.call_batch(int(B), lmax) for m in models))
     m0._ws.get(_ensemble_bytes(models, B, lmax))
+
+
+def reserve_ensemble_sets(model_lists, B: int, lmax: int):
+    """reserve_ensemble for several model lists of the same length that one caller alternates between (the control loop's
+    models, and the same list with overflowed half-precision models replaced by their fp32-range twins): the largest
+    workspace any of the lists - or any mix of their members - asks for, on the first model of each, so that whichever list a
+    call takes finds it allocated.  (A mix's widest activation buffer is that of one of the lists.)"""
+    lists = [list(ms) for ms in model_lists]
+    if any(m._h is None for ms in lists for m in ms):         # a generic program among them: one classify_raw per model
+        for m in {id(m): m for ms in lists for m in ms}.values():
+            m.reserve(B, lmax)
+        return
+    b = max(1, max(min(m.call_batch(int(B), lmax) for m in ms) for ms in lists))
+    need = max(_ensemble_bytes(ms, b, lmax) for ms in lists)
+    for m0 in {id(ms[0]): ms[0] for ms in lists}.values():
+        m0._ws.get(need)
 
 
 def classify_raw_ensemble(models, sig_dev: torch.Tensor, off_dev: torch.Tensor, len_dev: torch.Tensor,

@@ -95,14 +95,15 @@ def chunked_batches(n_batches: int, channels: int = 512, seed: int = 4242, chunk
 
 
 def run_replay(models, processor, batches, mode: str = "enrich", threshold: float = 0.9, skip: int = 3,
-               signal_cache: bool = True, client_cls=FakeClient) -> dict:
+               signal_cache: bool = True, client_cls=FakeClient, on_overflow: str = "warn") -> dict:
     """Drive SequencerControl.target over `batches`; returns counts and per-batch latency percentiles
-    (the first `skip` batches are warm-up: first launches, the signal store's first fill)."""
+    (the first `skip` batches are warm-up: first launches, the signal store's first fill).  `on_overflow`: the loop's policy
+    for batches in which a half-precision model overflowed (SequencerControl); its counters are in the result."""
     from .control import PHASES, SequencerControl
     client = client_cls(batches)
     with tempfile.TemporaryDirectory() as d:
         ctl = SequencerControl(client, models, processor, logging.getLogger("riser_amd.replay"),
-                               os.path.join(d, "out"), signal_cache=signal_cache)
+                               os.path.join(d, "out"), signal_cache=signal_cache, on_overflow=on_overflow)
         ctl.reserve(max(len(b) for b in batches))
         ctl.start()
         # the scripted batches are hundreds of thousands of long-lived Python objects that a live run never holds (its
@@ -143,4 +144,6 @@ def run_replay(models, processor, batches, mode: str = "enrich", threshold: floa
             "delta_reads": int(store.delta_reads), "overlap_mismatches": int(store.mismatches),
             "pcie_samples_uploaded": int(store.samples_uploaded),
             "pcie_samples_full_reupload": int(store.samples_presented),
-            "rejected": sum(len(r) for r in client.rejected), "finished": sum(len(r) for r in client.finished)}
+            "rejected": sum(len(r) for r in client.rejected), "finished": sum(len(r) for r in client.finished),
+            "on_overflow": on_overflow, "saturated_batches": int(ctl.saturated_batches),
+            "reclassified_batches": int(ctl.reclassified_batches), "withheld_batches": int(ctl.withheld_batches)}
