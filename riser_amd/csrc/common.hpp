@@ -64,7 +64,7 @@ struct Hooks {
     bool tail_debug = false;         // RS_TAIL_DEBUG: print every head / tail decision
     bool ring_tail_split = false;    // RS_RING_TAIL_SPLIT: head + tail launches for the 16-bit ring kernel too (measured: a wash)
     double tail_margin = 0.0;        // RS_TAIL_MARGIN: a head + tail split is taken when priced below this share of ONE launch (0: the kernels' own 0.97 / 0.92; tuning aid)
-    bool no_tail_split = false;      // RS_NO_TAIL_SPLIT: tiled conv layers (fp32 Winograd, 16-bit ring) always as ONE launch (tile_walk.hpp: plan_tail_split)
+    bool no_tail_split = false;      // RS_NO_TAIL_SPLIT: tiled conv layers (fp32 Winograd, 16-bit ring) always as ONE launch (tile_plan.hpp: plan_tiles)
     bool no_fuse0 = false;           // RS_NO_FUSE0: layer 0 as its own launch on the fp32 Winograd path
     bool no_stream_f32 = false;      // RS_NO_STREAM_F32 / _H16: tiled kernels instead of the streaming ones
     bool no_stream_h16 = false;
@@ -92,24 +92,14 @@ struct Hooks {
 };
 const Hooks& default_hooks();
 
-// The per-layer switches are lists "layer:value;..." or "layer:wm,wn,mt,nt;...".  The next entry of `layer` in the list from q
-// on: its numbers in v, and the text behind it to go on from (null: there is no further entry).  Where a layer is named more
-// than once its users take the last entry that suits them, so they ask until the answer is null.
+// The per-layer switches are lists "layer:value;..." or "layer:wm,wn,mt,nt;..." (the latter: tile_plan.hpp: next_layer_shape).  The
+// next entry of `layer` in the list from q on: its number in v, and the text behind it to go on from (null: there is no further
+// entry).  Where a layer is named more than once its users take the last entry that suits them, so they ask until the answer is null.
 inline const char* next_layer_value(const char* q, int layer, int* v) {
     for (; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr) {
         int l, x;
         if (sscanf(q, "%d:%d", &l, &x) == 2 && l == layer) {
             *v = x;
-            return strchr(q, ';') ? strchr(q, ';') + 1 : q + strlen(q);
-        }
-    }
-    return nullptr;
-}
-inline const char* next_layer_shape(const char* q, int layer, int* wm, int* wn, int* mt, int* nt) {
-    for (; q && *q; q = strchr(q, ';') ? strchr(q, ';') + 1 : nullptr) {
-        int l, x[4];
-        if (sscanf(q, "%d:%d,%d,%d,%d", &l, &x[0], &x[1], &x[2], &x[3]) == 5 && l == layer) {
-            *wm = x[0], *wn = x[1], *mt = x[2], *nt = x[3];
             return strchr(q, ';') ? strchr(q, ';') + 1 : q + strlen(q);
         }
     }
@@ -195,17 +185,11 @@ struct ConvLayerDev {
     float w_unscale = 1.0f;
     // rs_autotune: the measured-best entry of the kernel's tile-shape table per launch geometry (GEMM rows of the
     // launch -> shape index), consulted before the cost model; force_shape >= 0 overrides both while tuning
+    // (tile_plan.hpp: tuned_pick)
     int force_shape = -1;
     std::vector<std::pair<int64_t, int>> tuned;
     const Hooks* hooks = &default_hooks();    // the owning model's switches
 };
-
-inline int tuned_shape(const ConvLayerDev& L, int64_t rows) {
-    if (L.force_shape >= 0) return L.force_shape;
-    for (const auto& t : L.tuned)
-        if (t.first == rows) return t.second;
-    return -1;
-}
 
 int launch_conv_f32(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len,
                     int B, int P_in, int layer_index, int num_cu, const float* d_zero, int check_dead,
@@ -263,20 +247,21 @@ int launch_conv_thin_h16(const ConvLayerDev& L, const void* d_x, void* d_y, cons
 // RS_F16XF8 (conv_ring_f8.hip): split precision with the cross terms on the block-scaled 8-bit MFMA; F8 rows carry a scale plane
 int launch_conv_ring_f8(const ConvLayerDev& L, const void* d_x, void* d_y, const int32_t* d_len, int B, int P_in,
                         int layer_index, int num_cu, int check_dead, hipStream_t st, int* bm_out, int* bn_out);
-int conv_ring_f8_num_shapes();
-bool conv_ring_f8_shape_ok(const ConvLayerDev& L, int k);
 size_t f8_scale_offset(int64_t rows, int cp);     // byte offset of the scale plane behind `rows` F8 rows of cp 16-bit elements
 int f8_scale_stride(int64_t rows);                // rows per 64-channel panel of the plane (4 bytes each)
 size_t f8_scale_bytes(int64_t rows, int cp);
 int conv_ring_max_bn();
-int conv_ring_num_shapes();
-bool conv_ring_shape_ok(const ConvLayerDev& L, int k);
 int conv_f32_max_bn();
-// tile-shape tables of the tiled kernels (rs_autotune): number of entries, and whether entry k can run layer L
+// tile-shape tables of the tiled kernels (rs_autotune): number of entries, and whether entry k can run layer L - what a
+// tuned shape must satisfy (tile_plan.hpp: TileFamily::can_run)
 int conv_wino_num_shapes();
 bool conv_wino_shape_ok(const ConvLayerDev& L, int k);
 int conv_wino4_num_shapes();
 bool conv_wino4_shape_ok(const ConvLayerDev& L, int k);
+int conv_ring_num_shapes();
+bool conv_ring_shape_ok(const ConvLayerDev& L, int k);
+int conv_ring_f8_num_shapes();
+bool conv_ring_f8_shape_ok(const ConvLayerDev& L, int k);
 int conv_f32_kc_max();
 
 // rows of read b: (rbase[b] * P_last) + t, t < len[b] >> n_layers (P_last = rows per block of the last buffer)

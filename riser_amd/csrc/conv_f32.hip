@@ -27,6 +27,7 @@
 // LDS rows are KC+2 floats (= 2 mod 4): the 16 rows x 2 k-groups that a 32-lane half reads
 // with ds_read_b32 then fall in 32 distinct banks.
 #include "common.hpp"
+#include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
 #include <stdio.h>
@@ -439,14 +440,13 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f32_kernel(const ConvArgs a
 
 using KernelFn = void (*)(const ConvArgs);
 
-struct Shape {
-    int wm, wn, mt, nt;
+struct Shape : TileGeom {
     KernelFn fn[4];        // chunk = run-time, 16, 20, 24
 };
 
-#define RS_SHAPE(WM, WN, MT, NT)                                                                        \
-    {WM, WN, MT, NT, {conv_f32_kernel<WM, WN, MT, NT, 0>, conv_f32_kernel<WM, WN, MT, NT, 16>,        \
-                      conv_f32_kernel<WM, WN, MT, NT, 20>, conv_f32_kernel<WM, WN, MT, NT, 24>}}
+#define RS_SHAPE(WM, WN, MT, NT)                                                                          \
+    {{WM, WN, MT, NT}, {conv_f32_kernel<WM, WN, MT, NT, 0>, conv_f32_kernel<WM, WN, MT, NT, 16>,        \
+                        conv_f32_kernel<WM, WN, MT, NT, 20>, conv_f32_kernel<WM, WN, MT, NT, 24>}}
 const Shape kShapes[] = {
     // narrow outputs: all 8 waves stacked along rows
     RS_SHAPE(8, 1, 4, 2), RS_SHAPE(8, 1, 4, 3), RS_SHAPE(8, 1, 2, 5), RS_SHAPE(8, 1, 4, 5),
@@ -468,32 +468,23 @@ size_t lds_bytes(const Shape& s, int kc) {
     return 2 * (size_t)((bm + 2) + 3 * bn) * (kc + 2) * sizeof(float);
 }
 
-// Pick the tile shape for a layer launch.  Model: one persistent workgroup per CU; time =
-// rounds x (MFMA issue of a tile + per-item and per-tile overheads), in SIMD cycles.
-const Shape* choose_shape(int64_t rows, int n16 /* couts / 16 */, int kc, int nch, int num_cu, double* cost_out) {
-    const Shape* best = nullptr;
-    double best_cost = 1e300;
-    for (int k = 0; k < kNumShapes; ++k) {
-        const Shape& s = kShapes[k];
-        if (lds_bytes(s, kc) > 160 * 1024 || s.wm * s.wn != 8) continue;
-        const int bm = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-        const int64_t mtiles = (rows + bm - 1) / bm;
-        const int64_t ntiles = (n16 + bnt - 1) / bnt;
-        const int64_t tiles = mtiles * ntiles;
-        const int64_t rounds = (tiles + num_cu - 1) / num_cu;
-        const double steps = 3.0 * kc / 4.0;
-        // two waves share a SIMD: a k-step issues 2 * mt * nt MFMAs of 32 cycles on it; the
-        // (mt + nt) LDS reads per step and the barrier per item are partly exposed
-        const double item = steps * (2.0 * s.mt * s.nt * 32.0 + 6.0 * (s.mt + s.nt)) + 900.0;
-        const double tile = nch * item + 1500.0 + 40.0 * s.mt * s.nt;
-        const double cost = (double)rounds * tile;
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = &s;
-        }
-    }
-    if (cost_out) *cost_out = best_cost;
-    return best;
+// Tile cost for a layer launch.  Model: one persistent workgroup per CU; time =
+// rounds x (MFMA issue of a tile + per-item and per-tile overheads), in SIMD cycles.  Eight-wave shapes.
+double tile_cost(const Shape& s, int kc, int nch) {
+    if (lds_bytes(s, kc) > kConvLdsBudget || s.wm * s.wn != 8) return -1.0;
+    const double steps = 3.0 * kc / 4.0;
+    // two waves share a SIMD: a k-step issues 2 * mt * nt MFMAs of 32 cycles on it; the
+    // (mt + nt) LDS reads per step and the barrier per item are partly exposed
+    const double item = steps * (2.0 * s.mt * s.nt * 32.0 + 6.0 * (s.mt + s.nt)) + 900.0;
+    return nch * item + 1500.0 + 40.0 * s.mt * s.nt;
+}
+
+// the family as plan_tiles sees it (tile_plan.hpp), for a layer of nch chunks of kc channels.  Row unit: conv rows.  A forced shape
+// need only fit the LDS: the experimental four-wave entries, which the search never picks, can be forced (tests do).
+auto family(int kc, int nch) {
+    return tile_family(
+        kNumShapes, [](int k) -> const TileGeom& { return kShapes[k]; }, [=](int k) { return tile_cost(kShapes[k], kc, nch); },
+        NoThinFit{}, [=](int k) { return lds_bytes(kShapes[k], kc) <= kConvLdsBudget; });
 }
 
 }  // namespace
@@ -517,20 +508,14 @@ int launch_conv_f32(const ConvLayerDev& L, const float* d_x, float* d_y, const i
         return RS_ERR_ARG;
     }
     const int n16 = round_up(L.c_out, 16) / 16;
-    const Shape* s = choose_shape(rows64, n16, p.kc, p.nch, num_cu, nullptr);
-    {   // tuning aid: "layer:wm,wn,mt,nt;..."
-        int wm, wn, mt, nt;
-        for (const char* q = L.hooks->force_f32; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
-            for (int k = 0; k < kNumShapes; ++k)
-                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                    lds_bytes(kShapes[k], p.kc) <= 160 * 1024)
-                    s = &kShapes[k];
-    }
-    if (!s) {
+    // no rs_autotune picks for this kernel and never a split
+    const TilePlan plan = plan_tiles(family(p.kc, p.nch), rows64, n16, num_cu, {L.hooks->force_f32, layer_index}, {});
+    if (!plan.n_parts) {
         set_error("conv_f32: no tile shape fits (kc=%d)", p.kc);
         return RS_ERR_ARG;
     }
-    const int BM = s->wm * 16 * s->mt, BN = s->wn * 16 * s->nt;
+    const Shape* s = &kShapes[plan.part[0].shape];
+    const int BM = s->bm(), BN = s->bn();
     ConvArgs a;
     a.x = d_x;
     a.w = static_cast<const float*>(L.d_w);
@@ -549,8 +534,8 @@ int launch_conv_f32(const ConvLayerDev& L, const float* d_x, float* d_y, const i
     const size_t lds = lds_bytes(*s, p.kc);
     KernelFn fn = s->fn[p.kc == 16 ? 1 : p.kc == 20 ? 2 : p.kc == 24 ? 3 : 0];
     RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               160 * 1024));
-    const int n_mtiles = (a.rows_in + BM - 1) / BM, n_ntiles = (n16 * 16 + BN - 1) / BN;
+                               (int)kConvLdsBudget));
+    const int n_mtiles = plan.part[0].n_mtiles, n_ntiles = (n16 * 16 + BN - 1) / BN;
     const int64_t tiles = (int64_t)n_mtiles * n_ntiles;
     const unsigned grid = (unsigned)std::min<int64_t>(tiles, num_cu);
     a.walk = plan_walk(n_mtiles, n_ntiles, grid, num_cu, BM, 3.0 * BN, check_dead, !L.hooks->no_rect_order);

@@ -29,6 +29,7 @@
 // activation slab's first half.  IN_F8 = false reads split-precision rows ([hi x 32 | lo x 32] f16, three MFMAs: the first
 // layer of a run), OUT_F8 = false writes them (the last layer: the head reads hi + lo).
 #include "common.hpp"
+#include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
 #include <stdio.h>
@@ -684,8 +685,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_f8_kernel(const F8Args 
 
 using KernelFn = void (*)(const F8Args);
 
-struct Shape {
-    int wm, wn, mt, nt;
+struct Shape : TileGeom {
     KernelFn fn[3];     // [x3 -> f8, f8 -> f8, f8 -> x3]
 };
 
@@ -694,7 +694,7 @@ constexpr size_t lds_bytes_of(int bm, int bn, bool in_f8) {
 }
 
 #define RS_SHAPE(WM, WN, MT, NT)                                                                                         \
-    {WM, WN, MT, NT,                                                                                                     \
+    {{WM, WN, MT, NT},                                                                                                   \
      {conv_ring_f8_kernel<WM, WN, MT, NT, false, true>, conv_ring_f8_kernel<WM, WN, MT, NT, true, true>,                \
       conv_ring_f8_kernel<WM, WN, MT, NT, true, false>}}
 // even NT only: a scale block is two column groups of one wave
@@ -712,7 +712,7 @@ size_t lds_bytes(const Shape& s, bool in_f8) { return lds_bytes_of(s.wm * 16 * s
 // cost model in SIMD cycles per tile (conv_ring_h16.hip's, with this kernel's MFMA time per 128-byte panel and tap: an H
 // or an F sub-stage is MT x NT x 32 cycles for the two waves of a SIMD, a split-precision one 3 x 16 x 2)
 double tile_cost(const Shape& s, int n_panels, bool in_f8) {
-    if (lds_bytes(s, in_f8) > 160 * 1024) return -1.0;
+    if (lds_bytes(s, in_f8) > kConvLdsBudget) return -1.0;
     const int bm = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
     const double mfma = (in_f8 ? 2.0 : 3.0) * s.mt * s.nt * 16.0 * 2.0;
     const double dma = ((bm + 8) / 3.0 + bnt * 16.0) * 128.0 / 24.0;
@@ -724,34 +724,18 @@ double tile_cost(const Shape& s, int n_panels, bool in_f8) {
     return spill * (3.0 * n_panels * sub + 1500.0 + 60.0 * s.mt * s.nt * 2.0);
 }
 
-const Shape* choose_shape(int64_t rows, int cols, int n_panels, int num_cu, bool in_f8, double* cost_out = nullptr) {
-    const Shape* best = nullptr;
-    double best_cost = 1e300;
-    for (int k = 0; k < kNumShapes; ++k) {
-        const Shape& s = kShapes[k];
-        const double tile = tile_cost(s, n_panels, in_f8);
-        if (tile < 0) continue;
-        const int bm = s.wm * 16 * s.mt, bn = s.wn * s.nt * 16;
-        const int64_t mtiles = (rows + bm - 1) / bm;
-        const int64_t ntiles = (cols + bn - 1) / bn;
-        const int64_t tiles = mtiles * ntiles;
-        const int64_t rounds = (tiles + num_cu - 1) / num_cu;
-        const double cost = (double)rounds * tile;
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = &s;
-        }
-    }
-    if (cost_out) *cost_out = best_cost;
-    return best;
+// the family as plan_tiles sees it (tile_plan.hpp), for a layer of n_panels panels that reads F8 rows or not.  Row unit: conv
+// rows.  A forced or tuned shape need only fit the LDS.
+auto family(int n_panels, bool in_f8) {
+    return tile_family(
+        kNumShapes, [](int k) -> const TileGeom& { return kShapes[k]; }, [=](int k) { return tile_cost(kShapes[k], n_panels, in_f8); },
+        NoThinFit{}, [=](int k) { return lds_bytes(kShapes[k], in_f8) <= kConvLdsBudget; });
 }
 
 }  // namespace
 
 int conv_ring_f8_num_shapes() { return kNumShapes; }
-bool conv_ring_f8_shape_ok(const ConvLayerDev& L, int k) {
-    return k >= 0 && k < kNumShapes && lds_bytes(kShapes[k], L.f8_in) <= 160 * 1024;
-}
+bool conv_ring_f8_shape_ok(const ConvLayerDev& L, int k) { return k >= 0 && k < kNumShapes && family(L.ring_panels, L.f8_in).can_run(k); }
 
 // scale plane of a buffer of `rows` F8 rows of `cp` 16-bit elements: behind the rows, 256-byte aligned; one plane per 64-channel
 // panel, f8_scale_stride(rows) rows of 4 bytes each
@@ -780,20 +764,19 @@ int launch_conv_ring_f8(const ConvLayerDev& L, const void* d_x, void* d_y, const
     const int cols_out = L.cp_out / 2;      // channel slots of a row: F8 rows hold 128 halfwords per 64 slots, x3 rows 64 per 32
     const int cols_cover = out_f8 ? cols_out : round_up(L.c_out, 16);
     const int n_panels = L.ring_panels;
-    const Shape* s = choose_shape(rows64, cols_cover, n_panels, num_cu, in_f8);
-    {   // tuning aid: "layer:wm,wn,mt,nt;..."
-        int wm, wn, mt, nt;
-        for (const char* q = L.hooks->force_ring; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
-            for (int k = 0; k < kNumShapes; ++k)
-                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                    lds_bytes(kShapes[k], in_f8) <= 160 * 1024)
-                    s = &kShapes[k];
+    // the planner tiles 16-column groups; this kernel covers `cols_cover` channel slots: the same tiles as long as those are
+    // whole groups (F8 rows: panels of 64 slots; x3 rows: c_out rounded up to 16)
+    if (cols_cover % 16) {
+        set_error("conv_ring_f8: %d channel slots of layer %d are no whole 16-column groups", cols_cover, layer_index);
+        return RS_ERR_ARG;
     }
-    if (const int k = tuned_shape(L, rows64); k >= 0 && conv_ring_f8_shape_ok(L, k)) s = &kShapes[k];
-    if (!s) {
+    const TilePlan plan = plan_tiles(family(n_panels, in_f8), rows64, cols_cover / 16, num_cu,
+                                     {L.hooks->force_ring, layer_index, tuned_pick(L.force_shape, L.tuned, rows64)}, {});    // never split
+    if (!plan.n_parts) {
         set_error("conv_ring_f8: no tile shape fits");
         return RS_ERR_ARG;
     }
+    const Shape* s = &kShapes[plan.part[0].shape];
     F8Args a;
     a.x = static_cast<const unsigned short*>(d_x);
     a.w = static_cast<const unsigned short*>(L.d_w2);
@@ -827,8 +810,8 @@ int launch_conv_ring_f8(const ConvLayerDev& L, const void* d_x, void* d_y, const
     a.n_alloc = L.plan.n_alloc;
     a.n_reads = B;
     a.shift_out = layer_index + 1;
-    const int BM = s->wm * 16 * s->mt, BN = s->wn * 16 * s->nt;
-    const int n_mtiles = (int)((rows64 + BM - 1) / BM);
+    const int BM = s->bm(), BN = s->bn();
+    const int n_mtiles = plan.part[0].n_mtiles;
     const int n_ntiles = (cols_cover + BN - 1) / BN;
     a.cols_tiled = n_ntiles * BN;
     if (a.cols_tiled > L.plan.n_alloc) {
@@ -850,7 +833,7 @@ int launch_conv_ring_f8(const ConvLayerDev& L, const void* d_x, void* d_y, const
     if (!d_stamps) RS_HIP(hipMalloc(&d_stamps, 4 * 8 * 8 * 8));
     a.stamps = d_stamps;
 #endif
-    RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvLdsBudget));
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), lds_bytes(*s, in_f8), st, a);
     RS_HIP(hipGetLastError());
 #ifdef RS_RING_STAMPS

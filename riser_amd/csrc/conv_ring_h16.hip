@@ -25,6 +25,7 @@
 // The accumulation order over K is panel -> tap -> half, identical to the round-1 kernel with 64-channel panels: plain-mode
 // results are bit-identical to that kernel.
 #include "common.hpp"
+#include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
 #include <stdio.h>
@@ -696,8 +697,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_h16_kernel(const RingAr
 
 using KernelFn = void (*)(const RingArgs);
 
-struct Shape {
-    int wm, wn, mt, nt;
+struct Shape : TileGeom {
     KernelFn fn[2][2];     // [plain, x3][bf16, f16]
     KernelFn tail[2];      // x3 with the merged tail panel [bf16, f16]; null where the tail slabs do not fit the LDS
 };
@@ -707,14 +707,14 @@ constexpr size_t lds_bytes_of(int bm, int bn) { return (size_t)(2 * (bm + 8) + 3
 constexpr size_t lds_tail_bytes_of(int bm, int bn) { return lds_bytes_of(bm, bn) + (size_t)((bm + 8 + 31) / 32) * 1024 + (size_t)bn * kRowB; }
 template <int WM, int WN, int MT, int NT, bool F16>
 constexpr KernelFn tail_fn() {
-    if constexpr (lds_tail_bytes_of(WM * 16 * MT, WN * 16 * NT) <= 160 * 1024)
+    if constexpr (lds_tail_bytes_of(WM * 16 * MT, WN * 16 * NT) <= kConvLdsBudget)
         return conv_ring_h16_kernel<WM, WN, MT, NT, F16, true, true>;
     else
         return nullptr;
 }
 
 #define RS_SHAPE(WM, WN, MT, NT)                                                                                  \
-    {WM, WN, MT, NT,                                                                                              \
+    {{WM, WN, MT, NT},                                                                                            \
      {{conv_ring_h16_kernel<WM, WN, MT, NT, false, false>, conv_ring_h16_kernel<WM, WN, MT, NT, true, false>},   \
       {conv_ring_h16_kernel<WM, WN, MT, NT, false, true>, conv_ring_h16_kernel<WM, WN, MT, NT, true, true>}},     \
      {tail_fn<WM, WN, MT, NT, false>(), tail_fn<WM, WN, MT, NT, true>()}}
@@ -744,7 +744,7 @@ size_t lds_bytes(const Shape& s, bool tail = false) {
 // 300 x 7000, 128 x 16000 and 512 x 16000: the picks are within 1 % of the measured best of the table at all four.)
 // tail: the layer's last panel is the merged tail (n_panels counts it): one more pass of MFMAs per tile instead of three sub-stages
 double tile_cost(const Shape& s, int n_panels, bool x3, bool tail = false) {
-    if (lds_bytes(s, tail) > 160 * 1024 || (tail && !s.tail[0])) return -1.0;
+    if (lds_bytes(s, tail) > kConvLdsBudget || (tail && !s.tail[0])) return -1.0;
     const int bm = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
     const double mfma = (x3 ? 3.0 : 2.0) * s.mt * s.nt * 16.0 * 2.0;
     const double dma = ((bm + 8) / 3.0 + bnt * 16.0) * 128.0 / 24.0;
@@ -754,42 +754,28 @@ double tile_cost(const Shape& s, int n_panels, bool x3, bool tail = false) {
     return 3.0 * n_panels * sub + 1500.0 + 60.0 * s.mt * s.nt * (x3 ? 1.5 : 1.0);
 }
 
-const Shape* choose_shape(int64_t rows, int n16, int n_panels, int num_cu, bool x3, double* cost_out = nullptr, bool tail = false) {
-    const Shape* best = nullptr;
-    double best_cost = 1e300;
-    for (int k = 0; k < kNumShapes; ++k) {
-        const Shape& s = kShapes[k];
-        const double tile = tile_cost(s, n_panels, x3, tail);
-        if (tile < 0) continue;
-        const int bm = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-        const int64_t mtiles = (rows + bm - 1) / bm;
-        const int64_t ntiles = (n16 + bnt - 1) / bnt;
-        const int64_t tiles = mtiles * ntiles;
-        const int64_t rounds = (tiles + num_cu - 1) / num_cu;
-        const double cost = (double)rounds * tile;
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = &s;
-        }
-    }
-    if (cost_out) *cost_out = best_cost;
-    return best;
+// the family as plan_tiles sees it (tile_plan.hpp), for layer L in plain or split precision.  Row unit: conv rows.  A forced or
+// tuned shape must pass conv_ring_shape_ok, merged-tail rule included: a layer packed with the merged tail panel can only run
+// the shapes whose LDS holds the tail slabs.
+auto family(const ConvLayerDev& L, bool x3) {
+    const int n_panels = L.ring_panels;
+    const bool tail = x3 && L.ring_tail, packed_tail = L.ring_tail;
+    return tile_family(
+        kNumShapes, [](int k) -> const TileGeom& { return kShapes[k]; },
+        [=](int k) { return tile_cost(kShapes[k], n_panels, x3, tail); }, NoThinFit{},
+        [=](int k) { return lds_bytes(kShapes[k], packed_tail) <= kConvLdsBudget && (!packed_tail || kShapes[k].tail[0]); });
 }
 
 }  // namespace
 
 // the planner's own estimate (its cycles) of a launch over `rows` input rows with the best shape of the table
 double conv_ring_plan_cost(const ConvLayerDev& L, int64_t rows, int num_cu, bool x3) {
-    double cost = 1e300;
-    choose_shape(rows, round_up(L.c_out, 16) / 16, L.ring_panels, num_cu, x3, &cost, x3 && L.ring_tail);
-    return cost + 2500.0;
+    return choose_tile(family(L, x3), rows, round_up(L.c_out, 16) / 16, num_cu).cost + 2500.0;
 }
 
 int conv_ring_max_bn() { return 256; }
 int conv_ring_num_shapes() { return kNumShapes; }
-bool conv_ring_shape_ok(const ConvLayerDev& L, int k) {
-    return k >= 0 && k < kNumShapes && lds_bytes(kShapes[k], L.ring_tail) <= 160 * 1024 && (!L.ring_tail || kShapes[k].tail[0]);
-}
+bool conv_ring_shape_ok(const ConvLayerDev& L, int k) { return k >= 0 && k < kNumShapes && family(L, false).can_run(k); }
 
 int launch_conv_ring_h16(const ConvLayerDev& L, const void* d_x, void* d_y, const int32_t* d_len, int B, int P_in,
                          int layer_index, int num_cu, bool f16, bool x3, int check_dead, hipStream_t st, int* bm_out,
@@ -809,24 +795,15 @@ int launch_conv_ring_h16(const ConvLayerDev& L, const void* d_x, void* d_y, cons
     const int n16 = round_up(L.c_out, 16) / 16;
     const int n_panels = L.ring_panels;
     const bool tail = x3 && L.ring_tail;                              // the last of them is the merged tail panel
-    double single_cost = 0.0;
-    const Shape* s = choose_shape(rows64, n16, n_panels, num_cu, x3, &single_cost, tail);
-    bool pinned = false;                                            // a forced or tuned shape runs as one launch
-    {   // tuning aid: "layer:wm,wn,mt,nt;..."
-        int wm, wn, mt, nt;
-        for (const char* q = L.hooks->force_ring; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
-            for (int k = 0; k < kNumShapes; ++k)
-                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                    conv_ring_shape_ok(L, k)) {
-                    s = &kShapes[k];
-                    pinned = true;
-                }
-    }
-    if (const int k = tuned_shape(L, rows64); k >= 0 && conv_ring_shape_ok(L, k)) {
-        s = &kShapes[k];
-        pinned = true;
-    }
-    if (!s) {
+    // Head + tail launches are OFF for this kernel unless RS_RING_TAIL_SPLIT is set: measured over 24 random batch shapes
+    // (tools/tail_split_check.py, bf16x3) the split is worth -2.7 ... +2.3 % with a mean of 0.0 - this kernel's small tiles pay a
+    // prologue and an epilogue each that the planner's tile model does not price well enough to pick the winners - where the
+    // fp32 Winograd kernels gain up to 4 % and never lose.  Margin 0.92: splits the model prices within 8 % of one launch
+    // measured at -1 % (357 x 8615), the others at +1 ... +4.5 %.  The tail runs the shape the split was priced with.
+    const TilePlan plan = plan_tiles(family(L, x3), rows64, n16, num_cu, {L.hooks->force_ring, layer_index, tuned_pick(L.force_shape, L.tuned, rows64)},
+                                     {!L.hooks->no_tail_split && L.hooks->ring_tail_split,
+                                      L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.92, false});
+    if (!plan.n_parts) {
         set_error("conv_ring_h16: no tile shape fits");
         return RS_ERR_ARG;
     }
@@ -883,7 +860,7 @@ int launch_conv_ring_h16(const ConvLayerDev& L, const void* d_x, void* d_y, cons
         a.walk.m_base = m_base;
         KernelFn fn = tail ? sh.tail[f16 ? 1 : 0] : sh.fn[x3 ? 1 : 0][f16 ? 1 : 0];
         RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
+                                   (int)kConvLdsBudget));
         hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), lds_bytes(sh, tail), st, a);
         RS_HIP(hipGetLastError());
 #ifdef RS_RING_STAMPS
@@ -903,41 +880,17 @@ int launch_conv_ring_h16(const ConvLayerDev& L, const void* d_x, void* d_y, cons
 #endif
         return RS_OK;
     };
-    // Head + tail launches are OFF for this kernel unless RS_RING_TAIL_SPLIT is set: measured over 24 random batch shapes
-    // (tools/tail_split_check.py, bf16x3) the split is worth -2.7 ... +2.3 % with a mean of 0.0 - this kernel's small tiles pay a
-    // prologue and an epilogue each that the planner's tile model does not price well enough to pick the winners - where the
-    // fp32 Winograd kernels gain up to 4 % and never lose.
-    TailSplit split;
-    if (!pinned && !L.hooks->no_tail_split && L.hooks->ring_tail_split)
-        split = plan_tail_split(
-            kNumShapes, rows64, num_cu, single_cost, [&](int k) { return tile_cost(kShapes[k], n_panels, x3, tail); },
-            [&](int k) { return kShapes[k].wm * 16 * kShapes[k].mt; },
-            [&](int k) { return (n16 + kShapes[k].wn * kShapes[k].nt - 1) / (kShapes[k].wn * kShapes[k].nt); },
-            [&](int64_t r, double* c) {
-                const Shape* t = choose_shape(r, n16, n_panels, num_cu, x3, c, tail);
-                return t ? (int)(t - kShapes) : -1;
-            },
-            L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.92);      // this kernel's small tiles cost more than the model says (prologue + epilogue per tile): splits the
-                        // model prices within 8 % of one launch measured at -1 % (357 x 8615), the others at +1 ... +4.5 %
-    int BM, BN;
-    if (split.head_shape >= 0) {
-        const Shape &h = kShapes[split.head_shape], &t = kShapes[split.tail_shape];
-        if (L.hooks->tail_debug)
-            fprintf(stderr, "[tail-split] layer %d (ring): head %dx%dx%dx%d x %d row tiles, tail %dx%dx%dx%d; planned %.0f vs %.0f cycles\n",
-                    layer_index, h.wm, h.wn, h.mt, h.nt, split.head_mtiles, t.wm, t.wn, t.mt, t.nt, split.cost, single_cost);
-        BM = h.wm * 16 * h.mt;
-        BN = h.wn * 16 * h.nt;
-        int rc = launch_part(h, 0, split.head_mtiles);
-        if (rc != RS_OK) return rc;
-        const int m_base = split.head_mtiles * BM, tbm = t.wm * 16 * t.mt;
-        rc = launch_part(t, m_base, (a.rows_in - m_base + tbm - 1) / tbm);
-        if (rc != RS_OK) return rc;
-    } else {
-        BM = s->wm * 16 * s->mt;
-        BN = s->wn * 16 * s->nt;
-        const int rc = launch_part(*s, 0, (a.rows_in + BM - 1) / BM);
+    const Shape& h = kShapes[plan.part[0].shape];
+    if (plan.n_parts == 2 && L.hooks->tail_debug) {
+        const Shape& t = kShapes[plan.part[1].shape];
+        fprintf(stderr, "[tail-split] layer %d (ring): head %dx%dx%dx%d x %d row tiles, tail %dx%dx%dx%d; planned %.0f vs %.0f cycles\n",
+                layer_index, h.wm, h.wn, h.mt, h.nt, plan.part[0].n_mtiles, t.wm, t.wn, t.mt, t.nt, plan.cost, plan.single_cost);
+    }
+    for (int i = 0; i < plan.n_parts; ++i) {
+        const int rc = launch_part(kShapes[plan.part[i].shape], plan.part[i].m_base, plan.part[i].n_mtiles);
         if (rc != RS_OK) return rc;
     }
+    const int BM = h.bm(), BN = h.bn();       // a split reports the head's shape
     if (bm_out) *bm_out = BM;
     if (bn_out) *bn_out = BN;
     return RS_OK;

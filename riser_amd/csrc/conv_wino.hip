@@ -33,9 +33,7 @@
 // Schedule: persistent 8-wave workgroups, double-buffered LDS, register prefetch of the next
 // item distributed over the MFMA slots of the current one (conv_f32.hip has the rationale).
 #include "conv_wino_kernel.hpp"
-
-
-
+#include "tile_plan.hpp"
 
 // thin-launch fit of the planner (thin_tile_cost below): layer 11 at 16 ... 64 reads, every shape (tools/shape_sweep.py;
 // profiles/r05_wino_shape_sweep_16_to_512_reads.txt).  Launch, byte and per-tile terms are conv_wino4.hip's.
@@ -57,27 +55,26 @@ KernelFn conv_wino_thin_fn(int wm, int wn, int mt, int nt, int ki);
 
 namespace {
 
-
-struct Shape {
-    int wm, wn, mt, nt;
+struct Shape : TileGeom {
     KernelFn fn[3];        // chunk = 16, 20, 24
     KernelFn deep[3];      // the same tile with staging loads one item ahead (thin launches), or null
 };
-// layer 1 of the shipped net (20 -> 30 channels) with layer 0 folded into its staging
+// layer 1 of the shipped net (20 -> 30 channels) with layer 0 folded into its staging: this one instantiation, so the form pins its shape
 const KernelFn kFusedL1 = conv_wino_kernel<8, 1, 2, 2, 20, true>;
-constexpr int kFusedBMP = 8 * 16 * 2, kFusedBN = 32;
+constexpr TileGeom kFusedGeom = {8, 1, 2, 2};
+constexpr int kFusedBMP = kFusedGeom.bm(), kFusedBN = kFusedGeom.bn();
 
-#define RS_SHAPE(WM, WN, MT, NT)                                                                       \
-    {WM, WN, MT, NT, {conv_wino_kernel<WM, WN, MT, NT, 16>, conv_wino_kernel<WM, WN, MT, NT, 20>,     \
-                      conv_wino_kernel<WM, WN, MT, NT, 24>}, {nullptr, nullptr, nullptr}}
+#define RS_SHAPE(WM, WN, MT, NT)                                                                         \
+    {{WM, WN, MT, NT}, {conv_wino_kernel<WM, WN, MT, NT, 16>, conv_wino_kernel<WM, WN, MT, NT, 20>,     \
+                        conv_wino_kernel<WM, WN, MT, NT, 24>}, {nullptr, nullptr, nullptr}}
 // the thin-launch forms are instantiated in conv_wino_thin.hip
 #define RS_THIN3(WM, WN, MT, NT) \
     {conv_wino_thin_fn(WM, WN, MT, NT, 0), conv_wino_thin_fn(WM, WN, MT, NT, 1), conv_wino_thin_fn(WM, WN, MT, NT, 2)}
-#define RS_SHAPE_D(WM, WN, MT, NT)                                                                     \
-    {WM, WN, MT, NT, {conv_wino_kernel<WM, WN, MT, NT, 16>, conv_wino_kernel<WM, WN, MT, NT, 20>,     \
-                      conv_wino_kernel<WM, WN, MT, NT, 24>}, RS_THIN3(WM, WN, MT, NT)}
+#define RS_SHAPE_D(WM, WN, MT, NT)                                                                       \
+    {{WM, WN, MT, NT}, {conv_wino_kernel<WM, WN, MT, NT, 16>, conv_wino_kernel<WM, WN, MT, NT, 20>,     \
+                        conv_wino_kernel<WM, WN, MT, NT, 24>}, RS_THIN3(WM, WN, MT, NT)}
 // four-wave shapes exist in the one-item-ahead form only
-#define RS_SHAPE_4(WM, WN, MT, NT) {WM, WN, MT, NT, RS_THIN3(WM, WN, MT, NT), {nullptr, nullptr, nullptr}}
+#define RS_SHAPE_4(WM, WN, MT, NT) {{WM, WN, MT, NT}, RS_THIN3(WM, WN, MT, NT), {nullptr, nullptr, nullptr}}
 const Shape kShapes[] = {
     // all 8 waves stacked along pooled rows
     RS_SHAPE(8, 1, 2, 2), RS_SHAPE(8, 1, 2, 3), RS_SHAPE(8, 1, 2, 4), RS_SHAPE(8, 1, 1, 5), RS_SHAPE(8, 1, 1, 6),
@@ -108,7 +105,7 @@ size_t lds_bytes(const Shape& s, int kc) {
 // issue of a tile + per-item staging and barrier + per-tile epilogue), in SIMD cycles.  Full launches (at least one tile
 // per CU), eight-wave shapes; calibrated at B = 512.
 double tile_cost(const Shape& s, int kc, int nch) {
-    if (lds_bytes(s, kc) > 160 * 1024 || s.wm * s.wn != 8) return -1.0;
+    if (lds_bytes(s, kc) > kConvLdsBudget || s.wm * s.wn != 8) return -1.0;
     const int bmp = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
     const double slots = kc;                                    // 4 components x kc / 4 k-steps
     const double staged = ((2.0 * bmp + 2) + 4.0 * bnt * 16) * kc * 4.0;   // bytes per item
@@ -121,7 +118,7 @@ double tile_cost(const Shape& s, int kc, int nch) {
 // SIMD, staged bytes cost more the more CUs stream).  per_cu: workgroups of a four-wave shape resident on one CU.
 constexpr double kThinLaunch = RS_WINO_THIN_LAUNCH;
 double thin_tile_cost(const Shape& s, int kc, int nch, int per_cu, double fill) {
-    if (lds_bytes(s, kc) * per_cu > 160 * 1024) return -1.0;
+    if (lds_bytes(s, kc) * per_cu > kConvLdsBudget) return -1.0;
     const int bmp = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
     const double slots = kc;
     const double staged = ((2.0 * bmp + 2) + 4.0 * bnt * 16) * kc * 4.0 * per_cu;
@@ -131,52 +128,13 @@ double thin_tile_cost(const Shape& s, int kc, int nch, int per_cu, double fill) 
     return nch * item + RS_WINO_THIN_TILE + RS_WINO_THIN_TILE_MN * s.mt * s.nt;
 }
 
-// best shape for a launch over `rows_out` pooled rows: the B = 512 calibration over the eight-wave shapes; when that launch
-// leaves CUs idle (and thin is allowed), the thin-launch fit over every shape, four-wave ones at one or two per CU.
-const Shape* choose_shape(int64_t rows_out, int n16, int kc, int nch, int num_cu, double* cost_out, int* per_cu_out = nullptr,
-                          bool allow_thin = true, bool* thin_out = nullptr) {
-    const Shape* best = nullptr;
-    double best_cost = 1e300;
-    int best_per_cu = 1;
-    int64_t best_tiles = 0;
-    for (int k = 0; k < kNumShapes; ++k) {
-        const Shape& s = kShapes[k];
-        const double tile = tile_cost(s, kc, nch);
-        if (tile < 0) continue;
-        const int bmp = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-        const int64_t tiles = ((rows_out + bmp - 1) / bmp) * ((n16 + bnt - 1) / bnt);
-        const double cost = (double)((tiles + num_cu - 1) / num_cu) * tile;
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = &s;
-            best_tiles = tiles;
-        }
-    }
-    const bool thin = allow_thin && best && best_tiles < num_cu;
-    if (thin) {
-        best_cost = 1e300;
-        for (int k = 0; k < kNumShapes; ++k) {
-            const Shape& s = kShapes[k];
-            const int bmp = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-            const int64_t tiles = ((rows_out + bmp - 1) / bmp) * ((n16 + bnt - 1) / bnt);
-            const double fill = std::min(1.0, (double)tiles / num_cu);
-            for (int per_cu = 1; per_cu <= (s.wm * s.wn == 4 ? 2 : 1); ++per_cu) {
-                const double tile = thin_tile_cost(s, kc, nch, per_cu, fill);
-                if (tile < 0) continue;
-                const int64_t slots_ = (int64_t)num_cu * per_cu;
-                const double cost = (double)((tiles + slots_ - 1) / slots_) * tile;
-                if (cost < best_cost) {
-                    best_cost = cost;
-                    best = &s;
-                    best_per_cu = per_cu;
-                }
-            }
-        }
-    }
-    if (cost_out) *cost_out = best_cost;
-    if (per_cu_out) *per_cu_out = best_per_cu;
-    if (thin_out) *thin_out = thin;
-    return best;
+// the family as plan_tiles sees it (tile_plan.hpp), for a layer of nch chunks of kc channels.  Row unit: POOLED rows.  A forced
+// or tuned shape need only fit the LDS: the four-wave entries, which no full-launch search picks, can be pinned.
+auto family(int kc, int nch) {
+    return tile_family(
+        kNumShapes, [](int k) -> const TileGeom& { return kShapes[k]; }, [=](int k) { return tile_cost(kShapes[k], kc, nch); },
+        [=](int k, int per_cu, double fill) { return thin_tile_cost(kShapes[k], kc, nch, per_cu, fill); },
+        [=](int k) { return lds_bytes(kShapes[k], kc) <= kConvLdsBudget; });
 }
 
 }  // namespace
@@ -184,23 +142,19 @@ const Shape* choose_shape(int64_t rows_out, int n16, int kc, int nch, int num_cu
 int conv_wino_max_bn() { return 256; }
 // planner's estimate (SIMD cycles) of one launch with the best tile shape (compared with the small-batch kernel's in convnet_forward.hpp: select_kernel)
 double conv_wino_plan_cost(int64_t rows_out, int n16, int kc, int nch, int num_cu) {
-    double cost = 1e300;
-    choose_shape(rows_out, n16, kc, nch, num_cu, &cost, nullptr, false);
-    return cost;
+    return choose_tile(family(kc, nch), rows_out, n16, num_cu, false).cost;
 }
 // estimate of one launch INCLUDING its launch cost where the thin-launch fit applies (*thin_out): for the choice between
 // this kernel and conv_small_f32 (whose fit includes its launch as well)
 double conv_wino_launch_cost(int64_t rows_out, int n16, int kc, int nch, int num_cu, bool* thin_out) {
-    double cost = 1e300;
-    bool thin = false;
-    choose_shape(rows_out, n16, kc, nch, num_cu, &cost, nullptr, true, &thin);
-    if (thin_out) *thin_out = thin;
-    return thin ? cost + kThinLaunch : cost;
+    const TileChoice c = choose_tile(family(kc, nch), rows_out, n16, num_cu);
+    if (thin_out) *thin_out = c.thin;
+    return c.thin ? c.cost + kThinLaunch : c.cost;
 }
 int conv_wino_num_shapes() { return kNumShapes; }
 bool conv_wino_shape_ok(const ConvLayerDev& L, int k) {
     return k >= 0 && k < kNumShapes && (L.plan.kc == 16 || L.plan.kc == 20 || L.plan.kc == 24) &&
-           lds_bytes(kShapes[k], L.plan.kc) <= 160 * 1024;
+           family(L.plan.kc, L.plan.nch).can_run(k);
 }
 
 // layer 0 can be folded into this layer's staging when the layer is the shipped net's layer 1
@@ -224,38 +178,16 @@ int launch_conv_wino(const ConvLayerDev& L, const float* d_x, float* d_y, const 
         return RS_ERR_ARG;
     }
     const int n16 = round_up(L.c_out, 16) / 16;
-    double single_cost = 0.0;
-    int per_cu = 1;
-    const Shape* s = choose_shape(rows64 / 2, n16, p.kc, p.nch, num_cu, &single_cost, &per_cu);
-    bool pinned = false;                                          // a forced, fused or tuned shape runs as one launch
-    {   // tuning aid: "layer:wm,wn,mt,nt;..."
-        int wm, wn, mt, nt;
-        for (const char* q = L.hooks->force_wino; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
-            for (int k = 0; k < kNumShapes; ++k)
-                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                    lds_bytes(kShapes[k], p.kc) <= 160 * 1024) {
-                    s = &kShapes[k];
-                    pinned = true;
-                    per_cu = 1;
-                }
-    }
     const bool fused = fuse_xs != nullptr;
-    if (fused) {
-        pinned = true;
-        per_cu = 1;
-        if (!conv_wino_can_fuse0(L, P_in) || !fuse_w0) {
-            set_error("conv_wino: layer cannot take the fused layer-0 path");
-            return RS_ERR_ARG;
-        }
-        for (int k = 0; k < kNumShapes; ++k)
-            if (kShapes[k].wm == 8 && kShapes[k].wn == 1 && kShapes[k].mt == 2 && kShapes[k].nt == 2) s = &kShapes[k];
+    if (fused && (!conv_wino_can_fuse0(L, P_in) || !fuse_w0)) {
+        set_error("conv_wino: layer cannot take the fused layer-0 path");
+        return RS_ERR_ARG;
     }
-    if (const int k = tuned_shape(L, rows64); k >= 0 && conv_wino_shape_ok(L, k)) {
-        s = &kShapes[k];
-        pinned = true;
-        per_cu = 1;
-    }
-    if (!s) {
+    // the fused form exists as kFusedL1 only (launch_part): a tuned shape behind it changes the tile walk, not the kernel
+    const TilePlan plan = plan_tiles(family(p.kc, p.nch), rows64 / 2, n16, num_cu,
+                                     {L.hooks->force_wino, layer_index, tuned_pick(L.force_shape, L.tuned, rows64), fused ? &kFusedGeom : nullptr},
+                                     {!L.hooks->no_tail_split, L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.97, true});
+    if (!plan.n_parts) {
         set_error("conv_wino: no tile shape fits (kc=%d)", p.kc);
         return RS_ERR_ARG;
     }
@@ -304,7 +236,7 @@ int launch_conv_wino(const ConvLayerDev& L, const float* d_x, float* d_y, const 
         KernelFn fn = fused ? kFusedL1 : sh.fn[ki];
         if (KernelFn d = sh.deep[ki]; d && !fused && !L.hooks->no_deep_staging) fn = d;
         RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
+                                   (int)kConvLdsBudget));
         const int n_ntiles = (n16 * 16 + BN_ - 1) / BN_;
         const int64_t tiles = (int64_t)n_mtiles * n_ntiles;
         const int slots_ = num_cu * wg_per_cu;
@@ -316,42 +248,19 @@ int launch_conv_wino(const ConvLayerDev& L, const float* d_x, float* d_y, const 
         RS_HIP(hipGetLastError());
         return RS_OK;
     };
-    TailSplit split;
-    if (!pinned && !L.hooks->no_tail_split)
-        split = plan_tail_split(
-            kNumShapes, (int64_t)a.rows_out, num_cu, single_cost, [&](int k) { return tile_cost(kShapes[k], p.kc, p.nch); },
-            [&](int k) { return kShapes[k].wm * 16 * kShapes[k].mt; },
-            [&](int k) { return (n16 + kShapes[k].wn * kShapes[k].nt - 1) / (kShapes[k].wn * kShapes[k].nt); },
-            [&](int64_t r, double* c) {
-                // priced with the full-launch calibration like the head (one scale); the tail itself runs the shape the
-                // thin-launch fit picks for its rows
-                const Shape* t = choose_shape(r, n16, p.kc, p.nch, num_cu, c, nullptr, false);
-                return t ? (int)(t - kShapes) : -1;
-            },
-            L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.97);
-    int BMP, BN;
-    if (split.head_shape >= 0) {
-        const Shape& h = kShapes[split.head_shape];
-        BMP = h.wm * 16 * h.mt;
-        BN = h.wn * 16 * h.nt;
-        const int m_base = split.head_mtiles * BMP;
-        int tail_per_cu = 1;
-        const Shape* tp = choose_shape(a.rows_out - m_base, n16, p.kc, p.nch, num_cu, nullptr, &tail_per_cu);
-        const Shape& t = tp ? *tp : kShapes[split.tail_shape];
-        if (L.hooks->tail_debug)
-            fprintf(stderr, "[tail-split] layer %d: head %dx%dx%dx%d x %d row tiles, tail %dx%dx%dx%d (%d per CU); planned %.0f vs %.0f cycles\n",
-                    layer_index, h.wm, h.wn, h.mt, h.nt, split.head_mtiles, t.wm, t.wn, t.mt, t.nt, tail_per_cu, split.cost, single_cost);
-        int rc = launch_part(h, 0, split.head_mtiles, 1);
-        if (rc != RS_OK) return rc;
-        const int tbm = t.wm * 16 * t.mt;
-        rc = launch_part(t, m_base, (a.rows_out - m_base + tbm - 1) / tbm, tail_per_cu);
-        if (rc != RS_OK) return rc;
-    } else {
-        BMP = s->wm * 16 * s->mt;
-        BN = s->wn * 16 * s->nt;
-        const int rc = launch_part(*s, 0, (a.rows_out + BMP - 1) / BMP, per_cu);
+    const Shape& h = kShapes[plan.part[0].shape];
+    if (plan.n_parts == 2 && L.hooks->tail_debug) {
+        const Shape& t = kShapes[plan.part[1].shape];
+        fprintf(stderr, "[tail-split] layer %d: head %dx%dx%dx%d x %d row tiles, tail %dx%dx%dx%d (%d per CU); planned %.0f vs %.0f cycles\n",
+                layer_index, h.wm, h.wn, h.mt, h.nt, plan.part[0].n_mtiles, t.wm, t.wn, t.mt, t.nt, plan.part[1].per_cu, plan.cost,
+                plan.single_cost);
+    }
+    for (int i = 0; i < plan.n_parts; ++i) {
+        const TilePart& part = plan.part[i];
+        const int rc = launch_part(kShapes[part.shape], part.m_base, part.n_mtiles, part.per_cu);
         if (rc != RS_OK) return rc;
     }
+    const int BMP = h.bm(), BN = h.bn();      // a split reports the head's shape
     if (bm_out) *bm_out = 2 * BMP;          // reported in conv rows, like the direct kernels
     if (bn_out) *bn_out = BN;
     return RS_OK;

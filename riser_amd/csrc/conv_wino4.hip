@@ -25,6 +25,7 @@
 // with MT * NT <= 5 (6 x 4 accumulator registers per 16 x 16 sub-tile), and LDS capacity limits the channel
 // chunk to 16 or 20.  Used for the layers where the matrix pipe is the bound (chosen in rs_model_create).
 #include "common.hpp"
+#include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
 #include <stdio.h>
@@ -482,20 +483,19 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
 
 using KernelFn = void (*)(const Wino4Args);
 
-struct Shape {
-    int wm, wn, mt, nt;
+struct Shape : TileGeom {
     KernelFn fn[2];        // chunk = 16, 20
     KernelFn deep[2];      // the same tile with staging loads one item ahead (thin launches), or null
 };
 
 #define RS_SHAPE(WM, WN, MT, NT) \
-    {WM, WN, MT, NT, {conv_wino4_kernel<WM, WN, MT, NT, 16>, conv_wino4_kernel<WM, WN, MT, NT, 20>}, {nullptr, nullptr}}
-#define RS_SHAPE_D(WM, WN, MT, NT)                                                                     \
-    {WM, WN, MT, NT, {conv_wino4_kernel<WM, WN, MT, NT, 16>, conv_wino4_kernel<WM, WN, MT, NT, 20>}, \
+    {{WM, WN, MT, NT}, {conv_wino4_kernel<WM, WN, MT, NT, 16>, conv_wino4_kernel<WM, WN, MT, NT, 20>}, {nullptr, nullptr}}
+#define RS_SHAPE_D(WM, WN, MT, NT)                                                                       \
+    {{WM, WN, MT, NT}, {conv_wino4_kernel<WM, WN, MT, NT, 16>, conv_wino4_kernel<WM, WN, MT, NT, 20>}, \
      {conv_wino4_kernel<WM, WN, MT, NT, 16, true>, conv_wino4_kernel<WM, WN, MT, NT, 20, true>}}
 // four-wave shapes exist in the one-item-ahead form only
 #define RS_SHAPE_4(WM, WN, MT, NT) \
-    {WM, WN, MT, NT, {conv_wino4_kernel<WM, WN, MT, NT, 16, true>, conv_wino4_kernel<WM, WN, MT, NT, 20, true>}, {nullptr, nullptr}}
+    {{WM, WN, MT, NT}, {conv_wino4_kernel<WM, WN, MT, NT, 16, true>, conv_wino4_kernel<WM, WN, MT, NT, 20, true>}, {nullptr, nullptr}}
 const Shape kShapes[] = {
     // 512 x 96 (round 6): 36 accumulator tiles = 249 / 253 registers, no scratch; its LDS fits with chunks of 16 only (157 KB), so
     // rs_model_create's chunk choice moves layers 7 and 9 of the shipped net (22 and 48 column groups: 4 and 8 tiles of six) from
@@ -524,7 +524,7 @@ size_t lds_bytes(const Shape& s, int kc) {
 // input transform (12 VALU per MT, not hidden behind the MFMAs); per item: fixed cost, staging, and the activation slab's trip
 // from L2 / Infinity Cache (the weight slab is an L2 hit).  Calibrated on tools/shape_sweep.py (B = 512); eight-wave shapes.
 double tile_cost(const Shape& s, int kc, int nch) {
-    if (lds_bytes(s, kc) > 160 * 1024 || s.wm * s.wn != 8) return -1.0;
+    if (lds_bytes(s, kc) > kConvLdsBudget || s.wm * s.wn != 8) return -1.0;
     const int bg = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
     const double slots = 6.0 * kc / 4.0;
     const double staged = ((4.0 * bg + 2) + 6.0 * bnt * 16) * kc * 4.0;
@@ -541,7 +541,7 @@ double tile_cost(const Shape& s, int kc, int nch) {
 // workgroup's).  kThinLaunch: launch + first / last tile effects of the same fit (for the comparison with conv_small_f32).
 constexpr double kThinLaunch = 23500.0;
 double thin_tile_cost(const Shape& s, int kc, int nch, int per_cu, double fill) {
-    if (lds_bytes(s, kc) * per_cu > 160 * 1024) return -1.0;
+    if (lds_bytes(s, kc) * per_cu > kConvLdsBudget) return -1.0;
     const int bg = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
     const double slots = 6.0 * kc / 4.0;
     const double staged = ((4.0 * bg + 2) + 6.0 * bnt * 16) * kc * 4.0 * per_cu;
@@ -550,53 +550,13 @@ double thin_tile_cost(const Shape& s, int kc, int nch, int per_cu, double fill) 
     return nch * item - 467.0 + 554.0 * s.mt * s.nt;
 }
 
-// best shape for a launch over `groups` row units: the B = 512 calibration over the eight-wave shapes; when that launch
-// leaves CUs idle (and thin is allowed), the thin-launch fit over every shape, four-wave ones at one or two per CU.
-// *thin_out: which model *cost_out is in (their scales differ by up to 25 %: compare like with like).
-const Shape* choose_shape(int64_t groups, int n16, int kc, int nch, int num_cu, double* cost_out, int* per_cu_out = nullptr,
-                          bool allow_thin = true, bool* thin_out = nullptr) {
-    const Shape* best = nullptr;
-    double best_cost = 1e300;
-    int best_per_cu = 1;
-    int64_t best_tiles = 0;
-    for (int k = 0; k < kNumShapes; ++k) {
-        const Shape& s = kShapes[k];
-        const double tile = tile_cost(s, kc, nch);
-        if (tile < 0) continue;
-        const int bg = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-        const int64_t tiles = ((groups + bg - 1) / bg) * ((n16 + bnt - 1) / bnt);
-        const double cost = (double)((tiles + num_cu - 1) / num_cu) * tile;
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = &s;
-            best_tiles = tiles;
-        }
-    }
-    const bool thin = allow_thin && best && best_tiles < num_cu;
-    if (thin) {
-        best_cost = 1e300;
-        for (int k = 0; k < kNumShapes; ++k) {
-            const Shape& s = kShapes[k];
-            const int bg = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-            const int64_t tiles = ((groups + bg - 1) / bg) * ((n16 + bnt - 1) / bnt);
-            const double fill = std::min(1.0, (double)tiles / num_cu);
-            for (int per_cu = 1; per_cu <= (s.wm * s.wn == 4 ? 2 : 1); ++per_cu) {
-                const double tile = thin_tile_cost(s, kc, nch, per_cu, fill);
-                if (tile < 0) continue;
-                const int64_t slots_ = (int64_t)num_cu * per_cu;
-                const double cost = (double)((tiles + slots_ - 1) / slots_) * tile;
-                if (cost < best_cost) {
-                    best_cost = cost;
-                    best = &s;
-                    best_per_cu = per_cu;
-                }
-            }
-        }
-    }
-    if (cost_out) *cost_out = best_cost;
-    if (per_cu_out) *per_cu_out = best_per_cu;
-    if (thin_out) *thin_out = thin;
-    return best;
+// the family as plan_tiles sees it (tile_plan.hpp), for a layer of nch chunks of kc channels.  Row unit: GROUPS of four conv rows.
+// A forced or tuned shape need only fit the LDS: the four-wave entries, which no full-launch search picks, can be pinned.
+auto family(int kc, int nch) {
+    return tile_family(
+        kNumShapes, [](int k) -> const TileGeom& { return kShapes[k]; }, [=](int k) { return tile_cost(kShapes[k], kc, nch); },
+        [=](int k, int per_cu, double fill) { return thin_tile_cost(kShapes[k], kc, nch, per_cu, fill); },
+        [=](int k) { return lds_bytes(kShapes[k], kc) <= kConvLdsBudget; });
 }
 
 }  // namespace
@@ -604,25 +564,21 @@ const Shape* choose_shape(int64_t groups, int n16, int kc, int nch, int num_cu, 
 int conv_wino4_max_bn() { return 256; }
 int conv_wino4_num_shapes() { return kNumShapes; }
 bool conv_wino4_shape_ok(const ConvLayerDev& L, int k) {
-    return k >= 0 && k < kNumShapes && (L.plan.kc == 16 || L.plan.kc == 20) && lds_bytes(kShapes[k], L.plan.kc) <= 160 * 1024;
+    return k >= 0 && k < kNumShapes && (L.plan.kc == 16 || L.plan.kc == 20) && family(L.plan.kc, L.plan.nch).can_run(k);
 }
 
 // planner's estimate (SIMD cycles) of one launch with the best tile shape for this chunk size: lets
 // rs_model_create pick the channel chunk (which fixes the weight packing) with the tile shapes it enables in mind
 double conv_wino4_plan_cost(int64_t groups, int n16, int kc, int nch, int num_cu) {
-    double cost = 1e300;
-    choose_shape(groups, n16, kc, nch, num_cu, &cost, nullptr, false);
-    return cost;
+    return choose_tile(family(kc, nch), groups, n16, num_cu, false).cost;
 }
 
 // estimate of one launch INCLUDING its launch cost where the thin-launch fit applies (*thin_out), for the choice between
 // this kernel and conv_small_f32 (whose fit includes its launch as well)
 double conv_wino4_launch_cost(int64_t groups, int n16, int kc, int nch, int num_cu, bool* thin_out) {
-    double cost = 1e300;
-    bool thin = false;
-    choose_shape(groups, n16, kc, nch, num_cu, &cost, nullptr, true, &thin);
-    if (thin_out) *thin_out = thin;
-    return thin ? cost + kThinLaunch : cost;
+    const TileChoice c = choose_tile(family(kc, nch), groups, n16, num_cu);
+    if (thin_out) *thin_out = c.thin;
+    return c.thin ? c.cost + kThinLaunch : c.cost;
 }
 
 int launch_conv_wino4(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len, int B, int P_in,
@@ -641,27 +597,10 @@ int launch_conv_wino4(const ConvLayerDev& L, const float* d_x, float* d_y, const
     }
     const int n16 = round_up(L.c_out, 16) / 16;
     const int64_t groups = (rows64 + 3) / 4;
-    double single_cost = 0.0;
-    int per_cu = 1;
-    const Shape* s = choose_shape(groups, n16, p.kc, p.nch, num_cu, &single_cost, &per_cu);
-    bool pinned = false;                                          // a forced or tuned shape runs as one launch
-    {   // tuning aid: "layer:wm,wn,mt,nt;..."
-        int wm, wn, mt, nt;
-        for (const char* q = L.hooks->force_wino4; (q = next_layer_shape(q, layer_index, &wm, &wn, &mt, &nt));)
-            for (int k = 0; k < kNumShapes; ++k)
-                if (kShapes[k].wm == wm && kShapes[k].wn == wn && kShapes[k].mt == mt && kShapes[k].nt == nt &&
-                    lds_bytes(kShapes[k], p.kc) <= 160 * 1024) {
-                    s = &kShapes[k];
-                    pinned = true;
-                    per_cu = 1;
-                }
-    }
-    if (const int k = tuned_shape(L, rows64); k >= 0 && conv_wino4_shape_ok(L, k)) {
-        s = &kShapes[k];
-        pinned = true;
-        per_cu = 1;
-    }
-    if (!s) {
+    const TilePlan plan = plan_tiles(family(p.kc, p.nch), groups, n16, num_cu,
+                                     {L.hooks->force_wino4, layer_index, tuned_pick(L.force_shape, L.tuned, rows64)},
+                                     {!L.hooks->no_tail_split, L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.97, true});
+    if (!plan.n_parts) {
         set_error("conv_wino4: no tile shape fits (kc=%d)", p.kc);
         return RS_ERR_ARG;
     }
@@ -699,47 +638,24 @@ int launch_conv_wino4(const ConvLayerDev& L, const float* d_x, float* d_y, const
         KernelFn fn = sh.fn[p.kc == 16 ? 0 : 1];
         if (KernelFn d = sh.deep[p.kc == 16 ? 0 : 1]; d && !L.hooks->no_deep_staging) fn = d;
         RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
+                                   (int)kConvLdsBudget));
         hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * sh.wm * sh.wn), lds_bytes(sh, p.kc), st, a);
         RS_HIP(hipGetLastError());
         return RS_OK;
     };
-    TailSplit split;
-    if (!pinned && !L.hooks->no_tail_split)
-        split = plan_tail_split(
-            kNumShapes, groups, num_cu, single_cost, [&](int k) { return tile_cost(kShapes[k], p.kc, p.nch); },
-            [&](int k) { return kShapes[k].wm * 16 * kShapes[k].mt; },
-            [&](int k) { return (n16 + kShapes[k].wn * kShapes[k].nt - 1) / (kShapes[k].wn * kShapes[k].nt); },
-            [&](int64_t g, double* c) {
-                // priced with the full-launch calibration like the head (one scale); the tail itself runs the shape the
-                // thin-launch fit picks for its rows (never slower than this one)
-                const Shape* t = choose_shape(g, n16, p.kc, p.nch, num_cu, c, nullptr, false);
-                return t ? (int)(t - kShapes) : -1;
-            },
-            L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.97);
-    int BG, BN;
-    if (split.head_shape >= 0) {
-        const Shape& h = kShapes[split.head_shape];
-        BG = h.wm * 16 * h.mt;
-        BN = h.wn * 16 * h.nt;
-        const int m_base = split.head_mtiles * BG;
-        int tail_per_cu = 1;
-        const Shape* tp = choose_shape(groups - m_base, n16, p.kc, p.nch, num_cu, nullptr, &tail_per_cu);
-        const Shape& t = tp ? *tp : kShapes[split.tail_shape];
-        if (L.hooks->tail_debug)
-            fprintf(stderr, "[tail-split] layer %d: head %dx%dx%dx%d x %d row tiles, tail %dx%dx%dx%d (%d per CU); planned %.0f vs %.0f cycles\n",
-                    layer_index, h.wm, h.wn, h.mt, h.nt, split.head_mtiles, t.wm, t.wn, t.mt, t.nt, tail_per_cu, split.cost, single_cost);
-        int rc = launch_part(h, 0, split.head_mtiles, 1);
-        if (rc != RS_OK) return rc;
-        const int tbg = t.wm * 16 * t.mt;
-        rc = launch_part(t, m_base, (int)((groups - m_base + tbg - 1) / tbg), tail_per_cu);
-        if (rc != RS_OK) return rc;
-    } else {
-        BG = s->wm * 16 * s->mt;
-        BN = s->wn * 16 * s->nt;
-        const int rc = launch_part(*s, 0, (a.n_groups + BG - 1) / BG, per_cu);
+    const Shape& h = kShapes[plan.part[0].shape];
+    if (plan.n_parts == 2 && L.hooks->tail_debug) {
+        const Shape& t = kShapes[plan.part[1].shape];
+        fprintf(stderr, "[tail-split] layer %d: head %dx%dx%dx%d x %d row tiles, tail %dx%dx%dx%d (%d per CU); planned %.0f vs %.0f cycles\n",
+                layer_index, h.wm, h.wn, h.mt, h.nt, plan.part[0].n_mtiles, t.wm, t.wn, t.mt, t.nt, plan.part[1].per_cu, plan.cost,
+                plan.single_cost);
+    }
+    for (int i = 0; i < plan.n_parts; ++i) {
+        const TilePart& part = plan.part[i];
+        const int rc = launch_part(kShapes[part.shape], part.m_base, part.n_mtiles, part.per_cu);
         if (rc != RS_OK) return rc;
     }
+    const int BG = h.bm(), BN = h.bn();       // a split reports the head's shape
     if (bm_out) *bm_out = 4 * BG;           // reported in conv rows, like the other kernels
     if (bn_out) *bn_out = BN;
     return RS_OK;

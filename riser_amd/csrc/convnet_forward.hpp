@@ -52,8 +52,22 @@ enum class Kernel {
 inline bool reads_ring_packing(Kernel k) {
     return k == Kernel::ThinH16 || k == Kernel::RingF8 || k == Kernel::WresH16 || k == Kernel::RingH16;
 }
-// the tiled kernels with a table of tile shapes that rs_autotune times
-inline bool tunable(Kernel k) { return k == Kernel::Wino4 || k == Kernel::Wino2 || k == Kernel::RingF8 || k == Kernel::RingH16; }
+// the tile-shape table of a tiled kernel whose launcher consults rs_autotune's picks (tile_plan.hpp: tuned_pick): its size, and whether entry k can run layer L
+struct ShapeTable {
+    int (*num_shapes)();
+    bool (*shape_ok)(const ConvLayerDev& L, int k);
+};
+inline ShapeTable shape_table(Kernel k) {
+    switch (k) {
+        case Kernel::Wino4: return {conv_wino4_num_shapes, conv_wino4_shape_ok};
+        case Kernel::Wino2: return {conv_wino_num_shapes, conv_wino_shape_ok};
+        case Kernel::RingF8: return {conv_ring_f8_num_shapes, conv_ring_f8_shape_ok};
+        case Kernel::RingH16: return {conv_ring_num_shapes, conv_ring_shape_ok};
+        default: return {nullptr, nullptr};
+    }
+}
+// the kernels that rs_autotune times
+inline bool tunable(Kernel k) { return shape_table(k).num_shapes != nullptr; }
 
 // How layer 0 (one input channel) runs in this call: as its own launch, or folded into layer 1's kernel, which needs the
 // signal rows in the packed layout (always true via rs_classify)
@@ -138,12 +152,9 @@ Kernel select_kernel(const rs_model* m, int i, int NB, int P_in, const Fuse0& fu
 // a shape replaces the planner's choice for launches of `rows` GEMM rows only if it is > 3 % faster
 template <class Launch>
 int autotune_layer(rs_model* m, ConvLayerDev& L, Kernel kernel, int64_t rows, hipStream_t st, Launch launch_layer) {
-    const int n = kernel == Kernel::Wino4 ? conv_wino4_num_shapes() : kernel == Kernel::Wino2 ? conv_wino_num_shapes()
-                : kernel == Kernel::RingF8 ? conv_ring_f8_num_shapes() : conv_ring_num_shapes();
-    auto ok = [&](int k) {
-        return kernel == Kernel::Wino4 ? conv_wino4_shape_ok(L, k) : kernel == Kernel::Wino2 ? conv_wino_shape_ok(L, k)
-             : kernel == Kernel::RingF8 ? conv_ring_f8_shape_ok(L, k) : conv_ring_shape_ok(L, k);
-    };
+    const ShapeTable table = shape_table(kernel);
+    const int n = table.num_shapes();
+    auto ok = [&](int k) { return table.shape_ok(L, k); };
     hipEvent_t e0, e1;
     RS_HIP(hipEventCreate(&e0));
     RS_HIP(hipEventCreate(&e1));
