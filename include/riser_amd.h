@@ -540,6 +540,29 @@ typedef struct rs_gconv_plan {
 /* the tile a conv (riser/nets/cnn.py:12-18,43-65) of these sizes takes: a function of (c_in, c_out, k) alone, never of the
  * batch.  Needs no device.  RS_ERR_ARG for what rs_gconv_create refuses. */
 RS_API int rs_gconv_layer_plan(int c_in, int c_out, int k, rs_gconv_plan* out);
+/* Added after ABI 2.9 (rs_version stays 2.9): arithmetic of a generic ConvNet's convs (riser/nets/cnn.py:12-18,43-65).
+ * RS_BF16X3 runs every conv with c_in > 4 in split precision on the bf16 MFMA (csrc/gconv_x3.hip): each activation and weight
+ * is hi = bf16(v), lo = bf16(v - hi), a product is hi*hi + lo*hi + hi*lo on three v_mfma_f32_16x16x32_bf16 with fp32
+ * accumulation; bias, ReLU, the max-pool, the head and the activation buffers stay fp32, and a conv with c_in <= 4 (the first)
+ * keeps the fp32 kernel.  Every conv keeps the tile, the K chunk and the chunk count rs_gconv_layer_plan reports.  RS_F32 /
+ * RS_F32W go back to fp32 (the default), whose bits are those of a freshly created handle.  Any other dtype, or a null handle,
+ * returns RS_ERR_ARG and leaves the mode as it was; so does RS_BF16X3, before any device call, where the split slab and
+ * weight panel of a conv exceed 160 KB of LDS.  The split weights are packed on the first switch to RS_BF16X3 and freed by
+ * rs_gconv_destroy.  rs_gconv_workspace_bytes and rs_gconv_max_batch report the same figures in either mode, and a read in a
+ * ragged batch gets the bits it gets alone in either.  Not safe to call while a forward of the handle is being enqueued. */
+RS_API int rs_gconv_set_mode(rs_gconv* m, int dtype /* rs_dtype */);
+typedef struct rs_gconv_x3_plan {
+    int32_t steps;                  /* k-steps of 32 per K chunk: ceil(k kc / 32) */
+    int32_t slab_rows, slab_pitch;  /* rows (tile + halo + a zeroed spare row where a pair addresses tap k) x bf16 per row */
+    int32_t lds_bytes;              /* both planes of the slab and of one chunk's weight panel */
+    int64_t plane;                  /* bf16 per plane of the packed weights */
+} rs_gconv_x3_plan;
+/* The RS_BF16X3 form of a conv (riser/nets/cnn.py:12-18,43-65) with c_in > 4, on the host: its LDS layout and, where `w` (HOST
+ * fp32 [c_out, c_in, k]) and `packed` (2 * plane uint16) are both given, its split weights as the device reads them - planes
+ * [hi | lo], each [column block][chunk][column tile][step][lane][8]; lane (rl, kq) of step s holds column block * cols + 16 tile
+ * + rl, pair p = 4 s + kq, tap p / (kc / 8), channels chunk * kc + 8 (p % (kc / 8)) .. + 7; zero where the tap >= k, the channel
+ * >= c_in or the column >= c_out.  Needs no device.  RS_ERR_ARG for what rs_gconv_set_mode refuses and for c_in <= 4. */
+RS_API int rs_gconv_x3_layout(int c_in, int c_out, int k, rs_gconv_x3_plan* out, const float* w, uint16_t* packed);
 
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path

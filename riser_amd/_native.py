@@ -31,7 +31,7 @@ SYMBOLS = (
     "rs_crnn_create", "rs_crnn_destroy", "rs_crnn_min_length", "rs_crnn_steps", "rs_crnn_workspace_bytes", "rs_crnn_max_batch",
     "rs_crnn_forward_ragged", "rs_crnn_set_mode",
     "rs_gconv_create", "rs_gconv_destroy", "rs_gconv_min_length", "rs_gconv_max_batch", "rs_gconv_workspace_bytes",
-    "rs_gconv_forward_ragged", "rs_gconv_layer_plan",
+    "rs_gconv_forward_ragged", "rs_gconv_layer_plan", "rs_gconv_set_mode", "rs_gconv_x3_layout",
 )
 
 
@@ -53,6 +53,11 @@ RS_SEQ_FAMILIES = {1: "stem_pool", 2: "basic_block", 3: "bottleneck", 4: "conv_m
 class GConvPlan(C.Structure):
     """rs_gconv_plan: the tile a generic ConvNet's conv takes (rs_gconv_layer_plan)"""
     _fields_ = [(n, C.c_int32) for n in ("rows", "cols", "kc", "n_chunks", "vec", "lds_bytes", "shape", "reserved")]
+
+
+class GConvX3Plan(C.Structure):
+    """rs_gconv_x3_plan: the LDS layout of a conv's split-precision form (rs_gconv_x3_layout)"""
+    _fields_ = [(n, C.c_int32) for n in ("steps", "slab_rows", "slab_pitch", "lds_bytes")] + [("plane", C.c_int64)]
 
 
 class LayerInfo(C.Structure):
@@ -186,6 +191,10 @@ def lib():
     L.rs_gconv_forward_ragged.argtypes = [vp, vp, vp, i32, i32, vp, sz, vp, vp, vp]
     L.rs_gconv_layer_plan.restype = i32
     L.rs_gconv_layer_plan.argtypes = [i32, i32, i32, C.POINTER(GConvPlan)]
+    L.rs_gconv_set_mode.restype = i32
+    L.rs_gconv_set_mode.argtypes = [vp, i32]
+    L.rs_gconv_x3_layout.restype = i32
+    L.rs_gconv_x3_layout.argtypes = [i32, i32, i32, C.POINTER(GConvX3Plan), vp, vp]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32

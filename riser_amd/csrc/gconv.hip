@@ -18,8 +18,12 @@
 //
 // The tile shape and the chunk size depend on the conv's (c_in, c_out, k) only, never on the batch: every output element is
 // one fixed k-ordered MFMA chain and a read gets its solo bits in any batch, at any ld.
+//
+// rs_gconv_set_mode(m, RS_BF16X3) runs every conv with c_in > 4 on gconv_tile_x3_kernel instead (csrc/gconv_x3.hip: split
+// precision on the bf16 MFMA, the same plan, grid, buffers and epilogue); the other two kernels serve both modes.
 #include "common.hpp"
 #include "gconv/plan.hpp"
+#include "gconv_x3.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -243,6 +247,8 @@ struct ConvDev {
     TilePlan plan{};
     float* w = nullptr;
     float* b = nullptr;
+    X3Plan x3{};                                            // rs_gconv_set_mode: plan.vec == 4 only
+    unsigned short* wx = nullptr;                           // pack_weights_x3, from the first switch to RS_BF16X3 on
 };
 
 template <class T>
@@ -260,6 +266,7 @@ size_t round256(size_t v) { return (v + 255) / 256 * 256; }
 struct rs_gconv {
     int device = 0;
     int n_layers = 0, depth = 0, c_last = 0;
+    int mode = 0;               // rs_gconv_set_mode: 0 fp32 (f32-input MFMA), 1 split precision on the bf16 MFMA
     std::vector<rs::ConvDev> convs;
     float* d_fcw = nullptr;
     float* d_fcb = nullptr;
@@ -306,6 +313,7 @@ int rs_gconv_destroy(rs_gconv* m) {
     for (ConvDev& c : m->convs) {
         if (c.w) (void)hipFree(c.w);
         if (c.b) (void)hipFree(c.b);
+        if (c.wx) (void)hipFree(c.wx);
     }
     if (m->d_fcw) (void)hipFree(m->d_fcw);
     if (m->d_fcb) (void)hipFree(m->d_fcb);
@@ -380,6 +388,75 @@ int rs_gconv_create(const rs_gconv_conv* convs, int n_layers, int depth, const f
         return hip_fail(e, "rs_gconv_create upload");
     }
     *out = m;
+    return RS_OK;
+}
+
+int rs_gconv_set_mode(rs_gconv* m, int dtype) {
+    if (!m) {
+        set_error("rs_gconv_set_mode: null handle");
+        return RS_ERR_ARG;
+    }
+    if (dtype == RS_F32 || dtype == RS_F32W) {
+        m->mode = 0;
+        return RS_OK;
+    }
+    if (dtype != RS_BF16X3) {
+        set_error("rs_gconv_set_mode: a generic ConvNet runs in RS_F32 / RS_F32W (f32-input MFMA) or RS_BF16X3 (split "
+                  "precision on the bf16 MFMA)");
+        return RS_ERR_ARG;
+    }
+    for (size_t i = 0; i < m->convs.size(); ++i) {
+        ConvDev& c = m->convs[i];
+        if (c.plan.vec != 4) continue;
+        c.x3 = plan_x3(c.plan, c.k);
+        if (c.x3.lds_bytes > kLdsMax) {
+            set_error("rs_gconv_set_mode: conv %d (%d -> %d channels, kernel %d): the split slab and weight panel of one chunk "
+                      "take %d bytes of LDS, more than %d KB", (int)i, c.c_in, c.c_out, c.k, c.x3.lds_bytes, kLdsMax / 1024);
+            return RS_ERR_ARG;
+        }
+    }
+    DeviceGuard guard(m->device);
+    RS_HIP(guard.err);
+    for (ConvDev& c : m->convs) {
+        if (c.plan.vec != 4 || c.wx) continue;              // packed on the first switch, kept until rs_gconv_destroy
+        std::vector<float> packed((size_t)c.plan.ncb * c.plan.nchunk * c.plan.panel_floats);
+        RS_HIP(hipMemcpy(packed.data(), c.w, packed.size() * sizeof(float), hipMemcpyDeviceToHost));
+        const std::vector<float> w = unpack_weights(packed.data(), c.c_in, c.c_out, c.k, c.plan);
+        if (c.x3.lds_bytes > 64 * 1024) RS_HIP(gconv_x3_allow_lds(c.plan.shape, c.pool != 0, kLdsMax));
+        unsigned short* wx = nullptr;
+        hipError_t e = upload(&wx, pack_weights_x3(w.data(), c.c_in, c.c_out, c.k, c.plan));
+        if (e != hipSuccess) {
+            if (wx) (void)hipFree(wx);
+            return hip_fail(e, "rs_gconv_set_mode upload");
+        }
+        c.wx = wx;
+    }
+    m->mode = 1;
+    return RS_OK;
+}
+
+int rs_gconv_x3_layout(int c_in, int c_out, int k, rs_gconv_x3_plan* out, const float* w, uint16_t* packed) {
+    TilePlan p;
+    if (!out || c_in < 5 || c_out < 1 || k < 1 || (k & 1) == 0 || !plan_conv(c_in, c_out, k, &p)) {
+        set_error("rs_gconv_x3_layout: bad argument, c_in <= 4 (such a conv stays fp32), an even kernel, or a conv no tile shape "
+                  "holds in LDS");
+        return RS_ERR_ARG;
+    }
+    const X3Plan x = plan_x3(p, k);
+    if (x.lds_bytes > kLdsMax) {
+        set_error("rs_gconv_x3_layout: the split slab and weight panel of one chunk take %d bytes of LDS, more than %d KB",
+                  x.lds_bytes, kLdsMax / 1024);
+        return RS_ERR_ARG;
+    }
+    out->steps = x.steps;
+    out->slab_rows = x.slab_rows;
+    out->slab_pitch = x.xpitch;
+    out->lds_bytes = x.lds_bytes;
+    out->plane = (int64_t)p.ncb * p.nchunk * x.panel_half;
+    if (w && packed) {
+        const std::vector<uint16_t> v = pack_weights_x3(w, c_in, c_out, k, p);
+        memcpy(packed, v.data(), v.size() * sizeof(uint16_t));
+    }
     return RS_OK;
 }
 
@@ -460,9 +537,24 @@ int rs_gconv_forward_ragged(rs_gconv* m, const float* d_x, const int32_t* d_len,
             set_error("rs_gconv_forward_ragged: grid too large: split the batch");
             return RS_ERR_ARG;
         }
-        TileFn fn = tile_fn(c.plan.shape, c.plan.vec, c.pool != 0);
-        hipLaunchKernelGGL(fn, dim3((unsigned)grid, (unsigned)c.plan.ncb), dim3(256), (size_t)c.plan.lds_bytes, st, a);
-        RS_HIP(hipGetLastError());
+        if (m->mode == 1 && c.plan.vec == 4) {
+            GconvX3Args xa;
+            memset(&xa, 0, sizeof(xa));
+            xa.x = a.x; xa.y = a.y; xa.rows = a.rows; xa.b = a.b;
+            xa.w = c.wx;
+            xa.w_plane = (int64_t)c.plan.ncb * c.plan.nchunk * c.x3.panel_half;
+            xa.in_rows = a.in_rows; xa.in_pitch = a.in_pitch; xa.out_rows = a.out_rows; xa.out_pitch = a.out_pitch;
+            xa.c_in = a.c_in; xa.c_out = a.c_out; xa.k = a.k; xa.kc = a.kc; xa.nchunk = a.nchunk; xa.tiles = a.tiles;
+            xa.c8_shift = a.kc == 16 ? 1 : a.kc == 32 ? 2 : 3;
+            xa.steps = c.x3.steps; xa.xpitch = c.x3.xpitch; xa.slab_rows = c.x3.slab_rows;
+            xa.slab_half = c.x3.slab_half; xa.panel_half = c.x3.panel_half;
+            RS_HIP(gconv_x3_launch(c.plan.shape, c.pool != 0, xa, dim3((unsigned)grid, (unsigned)c.plan.ncb),
+                                   (size_t)c.x3.lds_bytes, st));
+        } else {
+            TileFn fn = tile_fn(c.plan.shape, c.plan.vec, c.pool != 0);
+            hipLaunchKernelGGL(fn, dim3((unsigned)grid, (unsigned)c.plan.ncb), dim3(256), (size_t)c.plan.lds_bytes, st, a);
+            RS_HIP(hipGetLastError());
+        }
         in = a.y;
         in_pitch = a.out_pitch;
     }

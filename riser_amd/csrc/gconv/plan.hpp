@@ -4,6 +4,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <vector>
 
@@ -104,6 +105,95 @@ inline std::vector<float> pack_weights(const float* w, int c_in, int c_out, int 
                                 const int ci = ch * p.kc + 4 * p.vec * g + p.vec * (lane >> 4) + sub;
                                 if (col < c_out && ci < c_in) out[o] = w[((size_t)col * c_in + ci) * k + tap];
                             }
+    return out;
+}
+
+// ---- split precision on the bf16 MFMA (gconv_x3.hip): the fp32 plan's shape, kc and nchunk, its own slab and packing ----
+// K of a chunk is tap-major over the chunk's kc channels, cut into k-steps of 32: lane (rl, kq) of step s takes pair
+// p = 4 s + kq, i.e. tap p / (kc / 8) and the 8 channels 8 (p % (kc / 8)) ..  Pairs behind the last tap (kc = 16 only: two
+// taps per step, k odd) meet zero weights and read a zeroed spare slab row.
+struct X3Plan {
+    int steps;                  // ceil(k kc / 32)
+    int xpitch;                 // bf16 per slab row: kc + 8, an odd number of 16-byte units
+    int slab_rows;              // tile rows + the last tap any pair addresses (k - 1, or k with a spare row)
+    int slab_half, panel_half;  // bf16 per plane: the slab; one chunk's panel of one column block
+    int lds_bytes;              // both planes of both
+};
+
+inline X3Plan plan_x3(const TilePlan& p, int k) {
+    const Shape& s = kShapes[p.shape];
+    const int c8n = p.kc / 8;
+    X3Plan x{};
+    x.steps = (k * p.kc + 31) / 32;
+    x.xpitch = (c8n % 2 == 0) ? p.kc + 8 : p.kc;
+    x.slab_rows = s.rows() + (4 * x.steps - 1) / c8n;
+    x.slab_half = x.slab_rows * x.xpitch;
+    x.panel_half = s.cols() * x.steps * 32;
+    x.lds_bytes = (x.slab_half + x.panel_half) * 4;
+    return x;
+}
+
+inline uint16_t bf16_rne(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+inline float bf16_val(uint16_t h) {
+    const uint32_t u = (uint32_t)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+// pack_weights undone: [c_out][c_in][k] from the packed fp32 panels (rs_gconv_set_mode reads them back from the device, so a
+// handle keeps no host copy of its weights)
+inline std::vector<float> unpack_weights(const float* packed, int c_in, int c_out, int k, const TilePlan& p) {
+    const Shape& s = kShapes[p.shape];
+    const int G = p.kc / (4 * p.vec), nct = s.cols() / 16;
+    std::vector<float> w((size_t)c_out * c_in * k, 0.0f);
+    size_t o = 0;
+    for (int nb = 0; nb < p.ncb; ++nb)
+        for (int ch = 0; ch < p.nchunk; ++ch)
+            for (int ct = 0; ct < nct; ++ct)
+                for (int tap = 0; tap < k; ++tap)
+                    for (int g = 0; g < G; ++g)
+                        for (int lane = 0; lane < 64; ++lane)
+                            for (int sub = 0; sub < p.vec; ++sub, ++o) {
+                                const int col = nb * s.cols() + 16 * ct + (lane & 15);
+                                const int ci = ch * p.kc + 4 * p.vec * g + p.vec * (lane >> 4) + sub;
+                                if (col < c_out && ci < c_in) w[((size_t)col * c_in + ci) * k + tap] = packed[o];
+                            }
+    return w;
+}
+
+// w [c_out][c_in][k] -> two planes [hi | lo] of bf16 bit patterns, each [column block][chunk][column tile][step][lane][8]: hi =
+// bf16(w), lo = bf16(w - hi), round to nearest even.  Lane (rl, kq), element e of step s: column block * cols + 16 tile + rl,
+// pair p = 4 s + kq, tap p / (kc / 8), channel chunk * kc + 8 (p % (kc / 8)) + e.  Zero where tap >= k, the channel >= c_in
+// or the column >= c_out.
+inline std::vector<uint16_t> pack_weights_x3(const float* w, int c_in, int c_out, int k, const TilePlan& p) {
+    const Shape& s = kShapes[p.shape];
+    const X3Plan x = plan_x3(p, k);
+    const int c8n = p.kc / 8, nct = s.cols() / 16;
+    const size_t plane = (size_t)p.ncb * p.nchunk * x.panel_half;
+    std::vector<uint16_t> out(2 * plane, 0);
+    size_t o = 0;
+    for (int nb = 0; nb < p.ncb; ++nb)
+        for (int ch = 0; ch < p.nchunk; ++ch)
+            for (int ct = 0; ct < nct; ++ct)
+                for (int st = 0; st < x.steps; ++st)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int e = 0; e < 8; ++e, ++o) {
+                            const int pr = 4 * st + (lane >> 4);
+                            const int tap = pr / c8n, ci = ch * p.kc + 8 * (pr % c8n) + e;
+                            const int col = nb * s.cols() + 16 * ct + (lane & 15);
+                            if (tap >= k || ci >= c_in || col >= c_out) continue;
+                            const float v = w[((size_t)col * c_in + ci) * k + tap];
+                            const uint16_t h = bf16_rne(v);
+                            out[o] = h;
+                            out[plane + o] = bf16_rne(v - bf16_val(h));
+                        }
     return out;
 }
 

@@ -4,7 +4,8 @@ The reference builds n_layers x [depth x (Conv1d(k, stride 1, 'same') + ReLU), M
 `gap_fc` classifier, AdaptiveAvgPool1d(1) + Linear (cnn.py:28-33).  The shipped shape (depth 1, kernel 3) has its own tuned
 path (Model); every other shape runs here: this module folds a reference state dict into a flat conv list (pure numpy, no
 GPU) and drives the device program of csrc/gconv.hip (rs_gconv_*): one tiled launch per conv with bias, ReLU and the layer's
-max-pool in its epilogue, reads of any length in one call.
+max-pool in its epilogue, reads of any length in one call.  dtype 'bf16x3' runs the convs with more than 4 input channels in
+split precision on the bf16 MFMA (csrc/gconv_x3.hip); fp32 is the default.
 """
 from __future__ import annotations
 
@@ -87,17 +88,40 @@ def layer_plan(c_in: int, c_out: int, k: int) -> dict:
     return {n: int(getattr(p, n)) for n, _ in nv.GConvPlan._fields_ if n != "reserved"}
 
 
+def x3_layout(c_in: int, c_out: int, k: int, w=None):
+    """the split-precision form of a conv with c_in > 4 (rs_gconv_x3_layout): dict(steps, slab_rows, slab_pitch, lds_bytes,
+    plane) and, given its weights w [c_out, c_in, k], `packed`: uint16 [2, plane], the hi and lo planes in the order the
+    device's lanes read them.  Needs no GPU."""
+    p = nv.GConvX3Plan()
+    lib = nv.lib()
+    nv.check(lib.rs_gconv_x3_layout(int(c_in), int(c_out), int(k), C.byref(p), None, None), "rs_gconv_x3_layout")
+    out = {n: int(getattr(p, n)) for n, _ in nv.GConvX3Plan._fields_}
+    if w is not None:
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        if w.shape != (c_out, c_in, k):
+            raise ValueError(f"w {w.shape}: expected ({c_out}, {c_in}, {k})")
+        packed = np.zeros((2, out["plane"]), np.uint16)
+        nv.check(lib.rs_gconv_x3_layout(int(c_in), int(c_out), int(k), C.byref(p), w.ctypes.data, packed.ctypes.data),
+                 "rs_gconv_x3_layout")
+        out["packed"] = packed
+    return out
+
+
+_MODES = {"f32": "f32", "f32w": "f32", "fp32": "f32", "bf16x3": "bf16x3"}
+
+
 class GConvNet:
     """A generic ConvNet on the device (rs_gconv_*): the surface Model drives for SeqNet - forward, forward_ragged,
-    max_batch.  fp32 on the f32-input MFMA only."""
+    max_batch.  fp32 on the f32-input MFMA (the default) or, dtype 'bf16x3', the convs with more than 4 input channels in
+    split precision on the bf16 MFMA."""
 
     ragged_ok = True
 
     def __init__(self, prog, device, dtype: str = "f32"):
-        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32"}.get(dtype)
-        if self.dtype is None:
-            raise ValueError(f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic fp32 "
-                             "conv program only")
+        self.dtype = "f32"
+        if _MODES.get(dtype) is None:
+            raise ValueError(f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic conv program "
+                             "in 'f32w' / 'f32' (f32-input MFMA) or 'bf16x3' (split precision on the bf16 MFMA) only")
         nv.require_gpu()
         d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
@@ -111,6 +135,21 @@ class GConvNet:
                                           prog["fc_b"].ctypes.data, self.device.index, C.byref(h)), "rs_gconv_create")
         self._h = h
         self._ws = None
+        if _MODES[dtype] != "f32":
+            try:
+                self.set_mode(dtype)
+            except Exception:
+                self.close()
+                raise
+
+    def set_mode(self, dtype: str):
+        """'f32' / 'f32w' / 'fp32' or 'bf16x3' (rs_gconv_set_mode): the arithmetic of the next forward.  fp32 after bf16x3
+        gives the bits of a fresh fp32 net; a refused dtype leaves the mode as it was."""
+        mode = _MODES.get(dtype)
+        if mode is None:
+            raise ValueError(f"dtype {dtype!r}: a generic ConvNet runs in 'f32w' / 'f32' or 'bf16x3'")
+        nv.check(nv.lib().rs_gconv_set_mode(self._h, nv.RS_BF16X3 if mode == "bf16x3" else nv.RS_F32), "rs_gconv_set_mode")
+        self.dtype = mode
 
     @property
     def min_length(self) -> int:

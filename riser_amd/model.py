@@ -171,16 +171,19 @@ class Model:
             self._h = None
             if any(int(k) % 2 == 0 for k in list(cnn.kernels)[: self.n_layers]):
                 raise ValueError("riser_amd: even conv kernels ('same' pads them asymmetrically) are not supported")
-            if dtype not in ("f32w", "f32"):
-                raise ValueError(f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic fp32 "
-                                 "conv program only")
-            if self.classifier == "gap_fc" and os.environ.get("RS_GCONV", "1") != "0" and "RS_SEQ_SCALAR" not in os.environ:
+            family = self.classifier == "gap_fc" and os.environ.get("RS_GCONV", "1") != "0" and "RS_SEQ_SCALAR" not in os.environ
+            if dtype not in ("f32w", "f32") and not (family and dtype == "bf16x3"):
+                raise ValueError(f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic conv "
+                                 "program in fp32 ('f32w' / 'f32') or, with the `gap_fc` head on the family of "
+                                 "csrc/gconv.hip, in 'bf16x3'")
+            if family:
                 from .gconv import GConvNet, build_gconv_program
-                self._seq = GConvNet(build_gconv_program(sd, cnn), device=self.device)
+                self._seq = GConvNet(build_gconv_program(sd, cnn), device=self.device, dtype=dtype)
+                self.dtype = self._seq.dtype
             else:
                 from .resnet import SeqNet, build_convnet_program
                 self._seq = SeqNet(*build_convnet_program(sd, cnn), device=self.device)
-            self.dtype = "f32"
+                self.dtype = "f32"
             self._ws = Workspace(self.device)
             return
         conv_w, conv_b = [], []

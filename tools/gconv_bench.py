@@ -6,7 +6,10 @@ tests/golden/convnet_variants.npz (channels 6-20, kernels 5-3-7-3) and a net of 
 list) with kernels 5.  Shapes: 512 x 16000, 512 x 4000, the live shape of 357 reads with distinct lengths around 8615, and
 1 / 16 reads.
     python tools/gconv_bench.py [steps] [--only LABEL] [--net depth2|shipped_k5|both] [--path gconv|seqnet|both]
---only / --path run one shape on one path (for a profiler run of its own)."""
+                                [--dtype f32|bf16x3|both]
+--only / --path run one shape on one path (for a profiler run of its own).  --dtype bf16x3 / both times the family in split
+precision on the bf16 MFMA (csrc/gconv_x3.hip) instead of / next to fp32: the seqnet path is left out, both modes are built
+in one process and timed shape by shape, interleaved, and "<shape>:f32/bf16x3" is the ratio of their ms per call."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -56,7 +59,7 @@ def _model(sd, cnn, dev, path):
     if path == "seqnet":
         os.environ["RS_GCONV"] = "0"
     try:
-        return Model(sd, synth.Config(cnn), None, "x", device=dev)
+        return Model(sd, synth.Config(cnn), None, "x", device=dev, dtype="bf16x3" if path == "gconv_x3" else "f32w")
     finally:
         os.environ.pop("RS_GCONV", None)
         if old is not None:
@@ -86,12 +89,14 @@ def run(steps=3, only=None, which=("depth2", "shipped_k5"), paths=("seqnet", "gc
             ln = torch.from_numpy(lens).to(dev)
             macs = sum(G.program_macs(prog, int(n)) for n in lens)
             for p, m in models.items():
-                ms = _time(lambda: m.forward_batch(x, lens, lens_dev=ln), steps if p == "gconv" or not ragged else 1, dev)
+                ms = _time(lambda: m.forward_batch(x, lens, lens_dev=ln), steps if p != "seqnet" or not ragged else 1, dev)
                 res[f"{label}:{p}"] = dict(ms=round(ms, 3), reads_per_s=round(B / (ms * 1e-3), 1),
                                            tflops=round(2 * macs / (ms * 1e-3) / 1e12, 3),
                                            frac_of_f32_mfma_peak=round(2 * macs / (ms * 1e-3) / 1e12 / PEAK_TF, 4))
-            if len(paths) == 2:
+            if "seqnet" in paths and "gconv" in paths:
                 res[f"{label}:seqnet/gconv"] = round(res[f"{label}:seqnet"]["ms"] / res[f"{label}:gconv"]["ms"], 3)
+            if "gconv" in paths and "gconv_x3" in paths:
+                res[f"{label}:f32/bf16x3"] = round(res[f"{label}:gconv"]["ms"] / res[f"{label}:gconv_x3"]["ms"], 3)
         for m in models.values():
             m.close()
         out[name] = res
@@ -105,6 +110,9 @@ if __name__ == "__main__":
     ap.add_argument("--only", default=None, choices=[s[0] for s in SHAPES])
     ap.add_argument("--net", choices=("depth2", "shipped_k5", "both"), default="both")
     ap.add_argument("--path", choices=("gconv", "seqnet", "both"), default="both")
+    ap.add_argument("--dtype", choices=("f32", "bf16x3", "both"), default="f32")
     args = ap.parse_args()
-    print(json.dumps(run(args.steps, args.only, ("depth2", "shipped_k5") if args.net == "both" else (args.net,),
-                         ("seqnet", "gconv") if args.path == "both" else (args.path,))))
+    paths = ("seqnet", "gconv") if args.path == "both" else (args.path,)
+    if args.dtype != "f32":                  # the family alone, in the modes asked for
+        paths = {"bf16x3": ("gconv_x3",), "both": ("gconv", "gconv_x3")}[args.dtype]
+    print(json.dumps(run(args.steps, args.only, ("depth2", "shipped_k5") if args.net == "both" else (args.net,), paths)))
