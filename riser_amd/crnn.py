@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _native as nv
+from ._family import FamilyNet
 
 CELLS = {"lstm": 0, "gru": 1}
 GATES = {"lstm": 4, "gru": 3}
@@ -135,24 +136,30 @@ class _Layer(C.Structure):
                [(n, C.c_void_p * 2) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
 
 
-class CRNNNet:
+class CRNNNet(FamilyNet):
     """A ConvRecNet on the device (rs_crnn_*): the surface Model drives for SeqNet - forward, forward_ragged, max_batch.
     dtype "f32" (also "f32w" / "fp32": fp32 on the f32-input MFMA, the default) or "f16x3": the gate GEMMs whose input is a
     hidden state (every recurrence, the input projection of every layer but the first) in split precision on the f16 MFMA,
-    everything else fp32 (rs_crnn_set_mode).  A hidden state lies in (-1, 1) and the weights are packed with a power-of-two
-    scale, so no f16 operand can overflow: the mode has no range check and never reports saturation."""
+    everything else fp32 (rs_crnn_set_mode, also between forwards).  A hidden state lies in (-1, 1) and the weights are packed
+    with a power-of-two scale, so no f16 operand can overflow: the mode has no range check and never reports saturation."""
 
-    ragged_ok = True
+    _PREFIX = "rs_crnn"
+    _MODES = {"f32": ("f32", nv.RS_F32), "f32w": ("f32", nv.RS_F32W), "fp32": ("f32", nv.RS_F32),
+              "f16x3": ("f16x3", nv.RS_F16X3)}
 
     def __init__(self, prog, device, dtype: str = "f32"):
-        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32", "f16x3": "f16x3"}.get(dtype)
-        if self.dtype is None:
-            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'f16x3' "
-                             "(split precision on the f16 MFMA for the gate GEMMs of hidden states)")
-        nv.require_gpu()
-        d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
-        self._keep = prog
+        super().__init__(prog, device, dtype)
+
+    @classmethod
+    def _refused_dtype(cls, dtype):
+        return (f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'f16x3' (split precision "
+                "on the f16 MFMA for the gate GEMMs of hidden states)")
+
+    def _no_workspace(self, B, ld):
+        return f"no workspace for {B} reads of {ld} samples (the network minimum is {self.min_length})"
+
+    def _create(self):
+        prog = self._keep
         convs = (_Conv * len(prog["convs"]))()
         for i, cv in enumerate(prog["convs"]):
             co, ci, k = cv["w"].shape
@@ -169,18 +176,7 @@ class CRNNNet:
         nv.check(nv.lib().rs_crnn_create(convs, len(convs), layers, len(layers), prog["fc_w"].ctypes.data,
                                          prog["fc_b"].ctypes.data, int(prog["out_dim"]), self.device.index, C.byref(h)),
                  "rs_crnn_create")
-        self._h = h
-        self._ws = None
-        if self.dtype == "f16x3":
-            self.set_mode("f16x3")
-
-    def set_mode(self, dtype: str):
-        """switch the arithmetic of the hidden-state gate GEMMs between forwards: "f32" or "f16x3" (rs_crnn_set_mode)"""
-        code = {"f32": nv.RS_F32, "f32w": nv.RS_F32W, "fp32": nv.RS_F32, "f16x3": nv.RS_F16X3}.get(dtype)
-        if code is None:
-            raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' or 'f16x3'")
-        nv.check(nv.lib().rs_crnn_set_mode(self._h, code), "rs_crnn_set_mode")
-        self.dtype = "f16x3" if code == nv.RS_F16X3 else "f32"
+        return h
 
     @property
     def min_length(self) -> int:
@@ -188,53 +184,3 @@ class CRNNNet:
 
     def steps(self, L: int) -> int:
         return int(nv.lib().rs_crnn_steps(self._h, int(L)))
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            nv.lib().rs_crnn_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def max_batch(self, L: int) -> int:
-        """largest batch of reads of (pitch) L samples one call can address: every activation buffer inside the 2 GiB
-        window (rs_crnn_max_batch); forward_ragged splits bigger batches"""
-        return max(1, int(nv.lib().rs_crnn_max_batch(self._h, int(L))))
-
-    def forward(self, x: torch.Tensor, return_logits: bool = False):
-        """x: fp32 device tensor [B, L] (one common length) -> fp32 [B, 2] on the device."""
-        B, L = x.shape
-        lens = torch.full((B,), L, dtype=torch.int32, device=self.device)
-        return self.forward_ragged(x, lens, return_logits)
-
-    def forward_ragged(self, x: torch.Tensor, lens_dev: torch.Tensor, return_logits: bool = False, out: torch.Tensor = None):
-        """x: fp32 device tensor [B, ld], read b = x[b, :lens_dev[b]] (int32 on the device) -> fp32 [B, 2] on the device;
-        every read's result is that of forward() on it alone, bit for bit."""
-        B, ld = x.shape
-        lib = nv.lib()
-        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-        mb = self.max_batch(ld)
-        if B > mb:                                  # reads are independent: equal parts, each inside the buffer window
-            parts = -(-B // mb)
-            step = -(-B // parts)
-            for s0 in range(0, B, step):
-                s1 = min(B, s0 + step)
-                r = self.forward_ragged(x[s0:s1], lens_dev[s0:s1], return_logits, out=probs[s0:s1])
-                if return_logits:
-                    logits[s0:s1] = r[1]
-            return (probs, logits) if return_logits else probs
-        need = lib.rs_crnn_workspace_bytes(self._h, B, ld)
-        if need == 0:
-            raise ValueError(f"no workspace for {B} reads of {ld} samples (the network minimum is {self.min_length})")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        nv.check(lib.rs_crnn_forward_ragged(self._h, x.data_ptr(), lens_dev.data_ptr(), B, ld, self._ws.data_ptr(),
-                                            self._ws.numel(), probs.data_ptr(), logits.data_ptr() if return_logits else None,
-                                            torch.cuda.current_stream(self.device).cuda_stream), "rs_crnn_forward_ragged")
-        return (probs, logits) if return_logits else probs

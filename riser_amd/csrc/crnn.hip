@@ -15,7 +15,7 @@
 //                      16w .. 16w + 15 and all gates of them.  For hidden <= 128 W_hh stays in VGPRs for the whole loop
 //                      (at most 4 gates x 32 k-steps = 128 floats per lane); wider layers read it from the cache.
 //                      No workgroup waits for another.
-//   crnn_head_kernel   Linear(out_dim -> 2) + softmax on the last step.
+//   last_row_head_kernel (family/head.hpp)   Linear(out_dim -> 2) + softmax on the last step.
 //
 // Ragged batches: the reads of a tile are aligned so that their recurrences end on the same step; a read that has not
 // started keeps h = c = 0 exactly (its update is skipped), the backward direction starts at each read's own last step.
@@ -29,6 +29,8 @@
 #include "common.hpp"
 #include "crnn/shared.hpp"
 #include "crnn/x3.hpp"
+#include "family/head.hpp"
+#include "family/host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -45,12 +47,6 @@ constexpr int kConvRows = 64;                       // conv positions per workgr
 constexpr int kConvLds = 64 * 1024;
 constexpr int kResHidden = 128;                     // hidden sizes up to this keep W_hh in VGPRs
 constexpr int kMaxHidden = 320;                     // h, h' and c of 16 reads in 64 KB of LDS
-constexpr int64_t kWindow = (int64_t(1) << 31) - 4096;     // every activation buffer stays inside 2 GiB
-
-inline int cp4(int c) { return (c + 3) & ~3; }
-inline int p16(int c) { return (c + 15) & ~15; }
-inline int lds_pitch(int cp) { return ((cp / 4) % 2 == 0) ? cp + 4 : cp; }
-
 
 // ------------------------------------------------------------------------------------------------ conv front
 struct ConvArgs {
@@ -335,58 +331,34 @@ __global__ __launch_bounds__(512) void crnn_rec_kernel(const RecArgs a) {
     }
 }
 
-// Linear(out_dim -> 2) + softmax (riser/model.py:27); a read too short for the net gets NaN (the host refuses it first)
-__global__ __launch_bounds__(256) void crnn_head_kernel(const float* __restrict__ f, int B, int pitch, int c, const float* __restrict__ fw,
-                                                        const float* __restrict__ fb, const int32_t* len, int ld, Lens ls,
-                                                        float* __restrict__ probs, float* __restrict__ logits) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const float* x = f + (int64_t)b * pitch;
-    float l0 = fb[0], l1 = fb[1];
-    for (int i = 0; i < c; ++i) {
-        l0 = fmaf(fw[i], x[i], l0);
-        l1 = fmaf(fw[c + i], x[i], l1);
-    }
-    if (crnn_len(len, b, ld, ls, ls.n) < 1) l0 = l1 = __builtin_nanf("");
-    const float mx = fmaxf(l0, l1);
-    const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-    const float s = e0 + e1;
-    probs[2 * b] = e0 / s;
-    probs[2 * b + 1] = e1 / s;
-    if (logits) {
-        logits[2 * b] = l0;
-        logits[2 * b + 1] = l1;
-    }
-}
+// the head's validity rule: a read too short for the net has no step and gets NaN (the host refuses it first)
+struct HasStep {
+    const int32_t* len;
+    int ld;
+    Lens ls;
+    __device__ bool operator()(int b) const { return !(crnn_len(len, b, ld, ls, ls.n) < 1); }
+};
 
 struct ConvDev {
     int c_in = 0, c_out = 0, k = 0, single = 0, cpi = 0, np = 0, ksteps = 0;
-    float* w = nullptr;
-    float* b = nullptr;
+    DevBuf<float> w, b;
 };
 
 struct LayerDev {
     int gru = 0, in_dim = 0, H = 0, Hp = 0, HT = 0, ndir = 1, relu = 0, N = 0, KSi = 0, KSh = 0;
-    float* wih[2] = {nullptr, nullptr};     // packed [N / 16][KSi][64]
-    float* bias[2] = {nullptr, nullptr};    // [N]
-    float* whh[2] = {nullptr, nullptr};     // packed [N / 16][KSh][64]
-    float* bhn[2] = {nullptr, nullptr};     // [Hp]
+    DevBuf<float> wih[2];       // packed [N / 16][KSi][64]
+    DevBuf<float> bias[2];      // [N]
+    DevBuf<float> whh[2];       // packed [N / 16][KSh][64]
+    DevBuf<float> bhn[2];       // [Hp]
     // f16x3 mode: the host weights and their f16 hi / lo fragments.  The host copies (W_hh, and W_ih of every layer but the
     // first: 4 bytes per weight, 1.6 MB for the bench LSTM) wait for the first rs_crnn_set_mode(RS_F16X3), which packs and
     // releases them; a handle that never leaves fp32 keeps them until rs_crnn_destroy
     std::vector<float> h_wih[2], h_whh[2];
-    u32x4* wih3[2] = {nullptr, nullptr};    // packed [N / 16][KSi3][hi, lo][64]; null for the first layer (fp32 projection)
-    u32x4* whh3[2] = {nullptr, nullptr};    // packed [N / 16][KSh3][hi, lo][64]
+    DevBuf<uint32_t> wih3[2];   // u32x4 [N / 16][KSi3][hi, lo][64]; null for the first layer (fp32 projection)
+    DevBuf<uint32_t> whh3[2];   // u32x4 [N / 16][KSh3][hi, lo][64]
     float inv_si[2] = {1.0f, 1.0f}, inv_sh[2] = {1.0f, 1.0f};
     int KSi3 = 0, KSh3 = 0;
 };
-
-template <class T>
-hipError_t upload(T** dst, const std::vector<T>& v) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T));
-    if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
 
 // w [rows = ng * H][K] (gate-major, as torch stores weight_ih / weight_hh) -> the MFMA B operand of every 16-column tile
 // of the padded gate layout (column gi * Hp + u) in the k order of the kernels: [N / 16][p16(K) / 4][64]
@@ -411,8 +383,7 @@ struct rs_crnn {
     std::vector<rs::ConvDev> convs;
     std::vector<rs::LayerDev> layers;
     rs::Lens ls{};
-    float* d_fcw = nullptr;
-    float* d_fcb = nullptr;
+    rs::DevBuf<float> d_fcw, d_fcb;
     int out_dim = 0;
     int min_len = 1;
     int x3 = 0;                 // 1: RS_F16X3
@@ -451,8 +422,6 @@ Plan plan(const rs_crnn* m, int ld) {
     return p;
 }
 
-size_t round256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 }  // namespace rs
 
@@ -463,22 +432,7 @@ extern "C" {
 int rs_crnn_destroy(rs_crnn* m) {
     if (!m) return RS_OK;
     DeviceGuard guard(m->device);
-    for (ConvDev& c : m->convs) {
-        if (c.w) (void)hipFree(c.w);
-        if (c.b) (void)hipFree(c.b);
-    }
-    for (LayerDev& l : m->layers)
-        for (int d = 0; d < 2; ++d) {
-            if (l.wih[d]) (void)hipFree(l.wih[d]);
-            if (l.bias[d]) (void)hipFree(l.bias[d]);
-            if (l.whh[d]) (void)hipFree(l.whh[d]);
-            if (l.bhn[d]) (void)hipFree(l.bhn[d]);
-            if (l.wih3[d]) (void)hipFree(l.wih3[d]);
-            if (l.whh3[d]) (void)hipFree(l.whh3[d]);
-        }
-    if (m->d_fcw) (void)hipFree(m->d_fcw);
-    if (m->d_fcb) (void)hipFree(m->d_fcb);
-    delete m;
+    delete m;                           // every device buffer is a DevBuf: freed with its holder
     return RS_OK;
 }
 
@@ -544,9 +498,9 @@ int rs_crnn_create(const rs_crnn_conv* convs, int n_conv, const rs_crnn_layer* l
                 for (int t = 0; t < c.k; ++t)
                     w[((size_t)t * cd.cpi + ci) * cd.np + co] = c.w[((size_t)co * c.c_in + ci) * c.k + t];
         }
-        e = upload(&cd.w, w);
-        if (e == hipSuccess) e = upload(&cd.b, b);
-        m->convs.push_back(cd);
+        e = upload(cd.w, w);
+        if (e == hipSuccess) e = upload(cd.b, b);
+        m->convs.push_back(std::move(cd));
         m->ls.k[i] = c.k;
     }
     for (int l = 0; l < n_layers && e == hipSuccess; ++l) {
@@ -565,7 +519,7 @@ int rs_crnn_create(const rs_crnn_conv* convs, int n_conv, const rs_crnn_layer* l
         ld.KSh = ld.Hp / 4;
         ld.KSi3 = p32(s.in_dim) / 32;
         ld.KSh3 = p32(ld.Hp) / 32;
-        m->layers.push_back(ld);
+        m->layers.push_back(std::move(ld));
         LayerDev& L = m->layers.back();
         for (int d = 0; d < L.ndir && e == hipSuccess; ++d) {
             std::vector<float> bias(L.N, 0.0f), bhn(L.Hp, 0.0f);
@@ -575,16 +529,16 @@ int rs_crnn_create(const rs_crnn_conv* convs, int n_conv, const rs_crnn_layer* l
                     bias[gi * L.Hp + u] = (L.gru && gi == 2) ? bi : bi + bh;     // GRU: r multiplies (W_hn h + b_hn)
                     if (L.gru && gi == 2) bhn[u] = bh;
                 }
-            e = upload(&L.wih[d], pack_gates(s.w_ih[d], ng, L.H, L.Hp, L.in_dim));
-            if (e == hipSuccess) e = upload(&L.whh[d], pack_gates(s.w_hh[d], ng, L.H, L.Hp, L.H));
-            if (e == hipSuccess) e = upload(&L.bias[d], bias);
-            if (e == hipSuccess) e = upload(&L.bhn[d], bhn);
+            e = upload(L.wih[d], pack_gates(s.w_ih[d], ng, L.H, L.Hp, L.in_dim));
+            if (e == hipSuccess) e = upload(L.whh[d], pack_gates(s.w_hh[d], ng, L.H, L.Hp, L.H));
+            if (e == hipSuccess) e = upload(L.bias[d], bias);
+            if (e == hipSuccess) e = upload(L.bhn[d], bhn);
             if (l > 0) L.h_wih[d].assign(s.w_ih[d], s.w_ih[d] + (size_t)ng * L.H * L.in_dim);
             L.h_whh[d].assign(s.w_hh[d], s.w_hh[d] + (size_t)ng * L.H * L.H);
         }
     }
-    if (e == hipSuccess) e = upload(&m->d_fcw, std::vector<float>(fc_w, fc_w + 2 * (size_t)out_dim));
-    if (e == hipSuccess) e = upload(&m->d_fcb, std::vector<float>(fc_b, fc_b + 2));
+    if (e == hipSuccess) e = upload(m->d_fcw, std::vector<float>(fc_w, fc_w + 2 * (size_t)out_dim));
+    if (e == hipSuccess) e = upload(m->d_fcb, std::vector<float>(fc_b, fc_b + 2));
     if (e != hipSuccess) {
         rs_crnn_destroy(m);
         return hip_fail(e, "rs_crnn_create upload");
@@ -635,8 +589,8 @@ int rs_crnn_set_mode(rs_crnn* m, int dtype) {
         for (size_t l = 0; l < m->layers.size() && e == hipSuccess; ++l) {
             LayerDev& L = m->layers[l];
             for (int d = 0; d < L.ndir && e == hipSuccess; ++d) {
-                if (!L.whh3[d]) e = upload(reinterpret_cast<uint32_t**>(&L.whh3[d]), pk[l].whh[d]);
-                if (e == hipSuccess && l > 0 && !L.wih3[d]) e = upload(reinterpret_cast<uint32_t**>(&L.wih3[d]), pk[l].wih[d]);
+                if (!L.whh3[d]) e = upload(L.whh3[d], pk[l].whh[d]);
+                if (e == hipSuccess && l > 0 && !L.wih3[d]) e = upload(L.wih3[d], pk[l].wih[d]);
                 L.inv_sh[d] = pk[l].inv_sh[d];
                 if (l > 0) L.inv_si[d] = pk[l].inv_si[d];
             }
@@ -680,45 +634,26 @@ size_t rs_crnn_workspace_bytes(const rs_crnn* m, int B, int ld) {
 int rs_crnn_max_batch(const rs_crnn* m, int ld) {
     if (!m || ld < m->min_len) return 0;
     const Plan p = plan(m, ld);
-    const size_t per = std::max(std::max(p.conv, p.xp), std::max(p.y, p.fin));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 30, kWindow / (int64_t)per));
+    return max_batch_of(std::max(std::max(p.conv, p.xp), std::max(p.y, p.fin)));
 }
 
 int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x, const int32_t* d_len, int B, int ld, void* d_ws, size_t ws_bytes,
                            float* d_probs, float* d_logits, void* stream) {
-    if (!m || !d_x || !d_len || !d_ws || !d_probs || B < 1 || ld < 1) {
-        set_error("rs_crnn_forward_ragged: bad argument");
-        return RS_ERR_ARG;
-    }
-    if (ld < m->min_len) {
-        set_error("rs_crnn_forward_ragged: reads of %d samples are shorter than the network minimum %d", ld, m->min_len);
-        return RS_ERR_LENGTH;
-    }
-    if (ws_bytes < rs_crnn_workspace_bytes(m, B, ld)) {
-        set_error("rs_crnn_forward_ragged: workspace too small");
-        return RS_ERR_WORKSPACE;
-    }
-    if (B > rs_crnn_max_batch(m, ld)) {
-        set_error("rs_crnn_forward_ragged: %d reads of %d samples outgrow the 2 GiB buffer window: split the batch "
-                  "(rs_crnn_max_batch)", B, ld);
-        return RS_ERR_ARG;
-    }
+    const int rc = check_ragged_call("rs_crnn_forward_ragged", "rs_crnn_max_batch", m, d_x, d_len, d_ws, d_probs, B, ld, ws_bytes, [&] {
+        return RaggedLimits{m->min_len, rs_crnn_workspace_bytes(m, B, ld), B <= rs_crnn_max_batch(m, ld)};
+    });
+    if (rc != RS_OK) return rc;
     DeviceGuard guard(m->device);
     RS_HIP(guard.err);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Plan p = plan(m, ld);
     std::vector<int> rows;
     conv_rows(m, ld, rows);
-    char* ws = static_cast<char*>(d_ws);
-    auto take = [&](size_t bytes) {
-        float* r = reinterpret_cast<float*>(ws);
-        ws += round256(bytes);
-        return r;
-    };
-    float* cbuf[2] = {take(B * p.conv), take(B * p.conv)};
-    float* xp[2] = {take(B * p.xp), take(B * p.xp)};
-    float* ybuf[2] = {take(B * p.y), take(B * p.y)};
-    float* fin = take(B * p.fin);
+    Carver ws(d_ws);
+    float* cbuf[2] = {ws.take(B * p.conv), ws.take(B * p.conv)};
+    float* xp[2] = {ws.take(B * p.xp), ws.take(B * p.xp)};
+    float* ybuf[2] = {ws.take(B * p.y), ws.take(B * p.y)};
+    float* fin = ws.take(B * p.fin);
 
     // conv front
     const float* in = d_x;
@@ -808,7 +743,7 @@ int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x, const int32_t* d_len, i
                 x.ld = ld;
                 x.len = d_len;
                 x.ls = m->ls;
-                x.w = L.wih3[d];
+                x.w = reinterpret_cast<const u32x4*>(L.wih3[d].p);
                 x.bias = L.bias[d];
                 x.inv_s = L.inv_si[d];
                 x.y = xp[d];
@@ -850,7 +785,7 @@ int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x, const int32_t* d_len, i
                 x.xp[d] = r.xp[d];
                 x.xp_rows[d] = r.xp_rows[d];
                 x.one_step[d] = r.one_step[d];
-                x.whh[d] = L.whh3[d];
+                x.whh[d] = reinterpret_cast<const u32x4*>(L.whh3[d].p);
                 x.inv_s[d] = L.inv_sh[d];
                 x.bhn[d] = L.bhn[d];
             }
@@ -886,8 +821,8 @@ int rs_crnn_forward_ragged(rs_crnn* m, const float* d_x, const int32_t* d_len, i
             in_dim_pitch = r.y_pitch;
         }
     }
-    hipLaunchKernelGGL(crnn_head_kernel, dim3((B + 255) / 256), dim3(256), 0, st, fin, B, cp4(m->out_dim), m->out_dim,
-                       m->d_fcw, m->d_fcb, d_len, ld, m->ls, d_probs, d_logits);
+    hipLaunchKernelGGL(last_row_head_kernel<HasStep>, dim3((B + 255) / 256), dim3(256), 0, st, fin, B, cp4(m->out_dim), m->out_dim,
+                       m->d_fcw, m->d_fcb, HasStep{d_len, ld, m->ls}, d_probs, d_logits);
     RS_HIP(hipGetLastError());
     return RS_OK;
 }

@@ -14,7 +14,7 @@
 //                          zero by select: what lies behind a read in its buffer is never multiplied.  Epilogue: bias + ReLU;
 //                          in the POOL form (a layer's last conv) the max of conv rows 2j and 2j + 1 - elements (0, 1) and
 //                          (2, 3) of one lane's accumulator - so that only pooled rows are written and no pool launch exists.
-//   gconv_head_kernel      GAP over a read's own rows + FC + softmax; a read with no row left gets NaN.
+//   gap_head_kernel        (family/head.hpp) GAP over a read's own rows + FC + softmax; a read with no row left gets NaN.
 //
 // The tile shape and the chunk size depend on the conv's (c_in, c_out, k) only, never on the batch: every output element is
 // one fixed k-ordered MFMA chain and a read gets its solo bits in any batch, at any ld.
@@ -22,6 +22,8 @@
 // rs_gconv_set_mode(m, RS_BF16X3) runs every conv with c_in > 4 on gconv_tile_x3_kernel instead (csrc/gconv_x3.hip: split
 // precision on the bf16 MFMA, the same plan, grid, buffers and epilogue); the other two kernels serve both modes.
 #include "common.hpp"
+#include "family/head.hpp"
+#include "family/host.hpp"
 #include "gconv/plan.hpp"
 #include "gconv_x3.hpp"
 
@@ -36,8 +38,6 @@ namespace {
 using namespace gconv;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int64_t kWindow = (int64_t(1) << 31) - 4096;     // every activation buffer stays inside 2 GiB
 
 __global__ __launch_bounds__(256) void gconv_lengths_kernel(const int32_t* __restrict__ len, int B, int ld, int n_pools,
                                                             int32_t* __restrict__ table) {
@@ -170,60 +170,6 @@ __global__ __launch_bounds__(256) void gconv_tile_kernel(const TileArgs a) {
     }
 }
 
-// GAP over the read's own T rows -> FC(c, 2) -> softmax (riser/nets/cnn.py:28-33, riser/model.py:27); one 256-thread workgroup
-// per read: wave w sums the rows t = w (mod 4) of each channel, LDS combines the four partial sums in a fixed order
-__global__ __launch_bounds__(256) void gconv_head_kernel(const float* __restrict__ x, int rows_pitch, int cp, int c,
-                                                         const float* __restrict__ fcw, const float* __restrict__ fcb,
-                                                         const int32_t* __restrict__ rows, float* __restrict__ probs,
-                                                         float* __restrict__ logits) {
-    __shared__ float part[4][64];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int T = as_const_len(rows)[b];
-    float a0 = 0.f, a1 = 0.f;
-    for (int c0 = 0; c0 < c; c0 += 64) {
-        const int ch = c0 + lane;
-        float s = 0.f;
-        if (ch < c) {
-            const float* col = x + (int64_t)b * rows_pitch * cp + ch;
-            int t = wave;
-            for (; t + 28 < T; t += 32) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = col[(int64_t)(t + 4 * u) * cp];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += v[u];
-            }
-            for (; t < T; t += 4) s += col[(int64_t)t * cp];
-        }
-        part[wave][lane] = s;
-        __syncthreads();
-        if (wave == 0 && ch < c) {
-            const float m = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (float)T;
-            a0 = fmaf(m, fcw[ch], a0);
-            a1 = fmaf(m, fcw[c + ch], a1);
-        }
-        __syncthreads();
-    }
-    if (wave != 0) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a0 += __shfl_xor(a0, d, 64);
-        a1 += __shfl_xor(a1, d, 64);
-    }
-    if (lane == 0) {
-        float l0 = a0 + fcb[0], l1 = a1 + fcb[1];
-        if (T < 1) l0 = l1 = __builtin_nanf("");            // shorter than the net's minimum: the reference's max_pool raises
-        const float mx = fmaxf(l0, l1);
-        const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-        probs[2 * b] = e0 / (e0 + e1);
-        probs[2 * b + 1] = e1 / (e0 + e1);
-        if (logits) {
-            logits[2 * b] = l0;
-            logits[2 * b + 1] = l1;
-        }
-    }
-}
-
 typedef void (*TileFn)(const TileArgs);
 
 template <int RT, int WGC, int WC>
@@ -245,20 +191,10 @@ TileFn tile_fn(int shape, int vec, bool pool) {
 struct ConvDev {
     int c_in = 0, c_out = 0, k = 0, pool = 0, level = 0;    // level: pools in front of this conv
     TilePlan plan{};
-    float* w = nullptr;
-    float* b = nullptr;
+    DevBuf<float> w, b;
     X3Plan x3{};                                            // rs_gconv_set_mode: plan.vec == 4 only
-    unsigned short* wx = nullptr;                           // pack_weights_x3, from the first switch to RS_BF16X3 on
+    DevBuf<uint16_t> wx;                                    // pack_weights_x3, from the first switch to RS_BF16X3 on
 };
-
-template <class T>
-hipError_t upload(T** dst, const std::vector<T>& v) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T));
-    if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
-
-size_t round256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 }  // namespace rs
@@ -268,8 +204,7 @@ struct rs_gconv {
     int n_layers = 0, depth = 0, c_last = 0;
     int mode = 0;               // rs_gconv_set_mode: 0 fp32 (f32-input MFMA), 1 split precision on the bf16 MFMA
     std::vector<rs::ConvDev> convs;
-    float* d_fcw = nullptr;
-    float* d_fcb = nullptr;
+    rs::DevBuf<float> d_fcw, d_fcb;
 };
 
 namespace rs {
@@ -310,14 +245,7 @@ int rs_gconv_layer_plan(int c_in, int c_out, int k, rs_gconv_plan* out) {
 int rs_gconv_destroy(rs_gconv* m) {
     if (!m) return RS_OK;
     DeviceGuard guard(m->device);
-    for (ConvDev& c : m->convs) {
-        if (c.w) (void)hipFree(c.w);
-        if (c.b) (void)hipFree(c.b);
-        if (c.wx) (void)hipFree(c.wx);
-    }
-    if (m->d_fcw) (void)hipFree(m->d_fcw);
-    if (m->d_fcb) (void)hipFree(m->d_fcb);
-    delete m;
+    delete m;                           // every device buffer is a DevBuf: freed with its holder
     return RS_OK;
 }
 
@@ -377,12 +305,12 @@ int rs_gconv_create(const rs_gconv_conv* convs, int n_layers, int depth, const f
         if (cd.plan.lds_bytes > 64 * 1024)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(tile_fn(cd.plan.shape, cd.plan.vec, cd.pool != 0)),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-        if (e == hipSuccess) e = upload(&cd.w, pack_weights(c.w, c.c_in, c.c_out, c.k, cd.plan));
-        if (e == hipSuccess) e = upload(&cd.b, b);
-        m->convs.push_back(cd);
+        if (e == hipSuccess) e = upload(cd.w, pack_weights(c.w, c.c_in, c.c_out, c.k, cd.plan));
+        if (e == hipSuccess) e = upload(cd.b, b);
+        m->convs.push_back(std::move(cd));
     }
-    if (e == hipSuccess) e = upload(&m->d_fcw, std::vector<float>(fc_w, fc_w + 2 * (size_t)m->c_last));
-    if (e == hipSuccess) e = upload(&m->d_fcb, std::vector<float>(fc_b, fc_b + 2));
+    if (e == hipSuccess) e = upload(m->d_fcw, std::vector<float>(fc_w, fc_w + 2 * (size_t)m->c_last));
+    if (e == hipSuccess) e = upload(m->d_fcb, std::vector<float>(fc_b, fc_b + 2));
     if (e != hipSuccess) {
         rs_gconv_destroy(m);
         return hip_fail(e, "rs_gconv_create upload");
@@ -423,13 +351,10 @@ int rs_gconv_set_mode(rs_gconv* m, int dtype) {
         RS_HIP(hipMemcpy(packed.data(), c.w, packed.size() * sizeof(float), hipMemcpyDeviceToHost));
         const std::vector<float> w = unpack_weights(packed.data(), c.c_in, c.c_out, c.k, c.plan);
         if (c.x3.lds_bytes > 64 * 1024) RS_HIP(gconv_x3_allow_lds(c.plan.shape, c.pool != 0, kLdsMax));
-        unsigned short* wx = nullptr;
-        hipError_t e = upload(&wx, pack_weights_x3(w.data(), c.c_in, c.c_out, c.k, c.plan));
-        if (e != hipSuccess) {
-            if (wx) (void)hipFree(wx);
-            return hip_fail(e, "rs_gconv_set_mode upload");
-        }
-        c.wx = wx;
+        DevBuf<uint16_t> wx;
+        const hipError_t e = upload(wx, pack_weights_x3(w.data(), c.c_in, c.c_out, c.k, c.plan));
+        if (e != hipSuccess) return hip_fail(e, "rs_gconv_set_mode upload");
+        c.wx = std::move(wx);
     }
     m->mode = 1;
     return RS_OK;
@@ -475,35 +400,22 @@ size_t rs_gconv_workspace_bytes(const rs_gconv* m, int B, int ld) {
 
 int rs_gconv_max_batch(const rs_gconv* m, int ld) {
     if (!m || ld < (1 << m->n_layers)) return 0;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 30, kWindow / (int64_t)per_read_bytes(m, ld)));
+    return max_batch_of(per_read_bytes(m, ld));
 }
 
 int rs_gconv_forward_ragged(rs_gconv* m, const float* d_x, const int32_t* d_len, int B, int ld, void* d_ws, size_t ws_bytes,
                             float* d_probs, float* d_logits, void* stream) {
-    if (!m || !d_x || !d_len || !d_ws || !d_probs || B < 1 || ld < 1) {
-        set_error("rs_gconv_forward_ragged: bad argument");
-        return RS_ERR_ARG;
-    }
-    if (ld < (1 << m->n_layers)) {
-        set_error("rs_gconv_forward_ragged: reads of %d samples are shorter than the network minimum %d", ld, 1 << m->n_layers);
-        return RS_ERR_LENGTH;
-    }
-    if (ws_bytes < rs_gconv_workspace_bytes(m, B, ld)) {
-        set_error("rs_gconv_forward_ragged: workspace too small");
-        return RS_ERR_WORKSPACE;
-    }
-    if (B > rs_gconv_max_batch(m, ld)) {
-        set_error("rs_gconv_forward_ragged: %d reads of %d samples outgrow the 2 GiB buffer window: split the batch "
-                  "(rs_gconv_max_batch)", B, ld);
-        return RS_ERR_ARG;
-    }
+    const int rc = check_ragged_call("rs_gconv_forward_ragged", "rs_gconv_max_batch", m, d_x, d_len, d_ws, d_probs, B, ld, ws_bytes, [&] {
+        return RaggedLimits{1 << m->n_layers, rs_gconv_workspace_bytes(m, B, ld), B <= rs_gconv_max_batch(m, ld)};
+    });
+    if (rc != RS_OK) return rc;
     DeviceGuard guard(m->device);
     RS_HIP(guard.err);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t buf_bytes = round256((size_t)B * per_read_bytes(m, ld));
-    char* ws = static_cast<char*>(d_ws);
-    float* bufs[2] = {reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + buf_bytes)};
-    int32_t* table = reinterpret_cast<int32_t*>(ws + 2 * buf_bytes);
+    const size_t buf_bytes = (size_t)B * per_read_bytes(m, ld);
+    Carver ws(d_ws);
+    float* bufs[2] = {ws.take(buf_bytes), ws.take(buf_bytes)};
+    int32_t* table = ws.take<int32_t>((size_t)(m->n_layers + 1) * B * sizeof(int32_t));
 
     hipLaunchKernelGGL(gconv_lengths_kernel, dim3((B + 255) / 256), dim3(256), 0, st, d_len, B, ld, m->n_layers, table);
     RS_HIP(hipGetLastError());
@@ -558,7 +470,7 @@ int rs_gconv_forward_ragged(rs_gconv* m, const float* d_x, const int32_t* d_len,
         in = a.y;
         in_pitch = a.out_pitch;
     }
-    hipLaunchKernelGGL(gconv_head_kernel, dim3(B), dim3(256), 0, st, in, ld >> m->n_layers, in_pitch, m->c_last, m->d_fcw,
+    hipLaunchKernelGGL(gap_head_kernel<true>, dim3(B), dim3(256), 0, st, in, ld >> m->n_layers, in_pitch, m->c_last, m->d_fcw,
                        m->d_fcb, table + (size_t)m->n_layers * B, d_probs, d_logits);
     RS_HIP(hipGetLastError());
     return RS_OK;

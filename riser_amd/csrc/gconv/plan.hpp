@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "../family/host.hpp"      // cp4, p16
+
 namespace rs {
 namespace gconv {
 
@@ -15,9 +17,6 @@ constexpr int kMaxPools = 16;                       // rows of the length table 
 constexpr int kLdsPrefer = 52 * 1024;               // three workgroups per CU
 constexpr int kLdsMax = 160 * 1024;                 // one workgroup per CU
 constexpr int kDeepFrom = 256;                      // p16(c_out) beyond this: 16-row tiles (wide layers sit deep, where reads are short)
-
-inline int cp4(int c) { return (c + 3) & ~3; }
-inline int p16(int c) { return (c + 15) & ~15; }
 
 // (row tiles, wave columns, column tiles per wave) of gconv_tile_kernel; a workgroup is 4 waves laid out (4 / wgc) x wgc
 struct Shape {

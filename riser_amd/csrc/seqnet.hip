@@ -258,8 +258,8 @@ int seqnet_forward_impl(rs_seqnet* m, const float* d_x, const int32_t* d_len, in
         }
         RS_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(seq_head_kernel, dim3(B), dim3(256), 0, st, buf(last), shp[last_op].t_out, m->c_last, m->d_fcw, m->d_fcb,
-                       d_probs, d_logits, rows_after(last_op));
+    hipLaunchKernelGGL(gap_head_kernel<false>, dim3(B), dim3(256), 0, st, buf(last), shp[last_op].t_out, m->c_last, m->c_last,
+                       m->d_fcw, m->d_fcb, rows_after(last_op), d_probs, d_logits);
     RS_HIP(hipGetLastError());
     return RS_OK;
 }

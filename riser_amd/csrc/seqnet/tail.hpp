@@ -1,6 +1,8 @@
-// Sequential conv programs (seqnet.hip): the tail of a program - unfused max-pool, GAP + FC + softmax head, ragged lengths.
+// Sequential conv programs (seqnet.hip): the tail of a program - unfused max-pool, ragged lengths; the GAP + FC + softmax head is
+// family/head.hpp: gap_head_kernel.
 #pragma once
 #include "../common.hpp"
+#include "../family/head.hpp"
 
 namespace rs {
 namespace {
@@ -17,61 +19,6 @@ __global__ __launch_bounds__(256) void seq_maxpool_kernel(const float* __restric
     if (t0 >= 0 && t0 < T_in) v = fmaxf(v, x[((int64_t)b * T_in + t0) * c + ch]);
     if (t1 >= 0 && t1 < T_in) v = fmaxf(v, x[((int64_t)b * T_in + t1) * c + ch]);
     y[g] = v;
-}
-
-// GAP over T rows -> FC(c, 2) -> softmax; one 256-thread workgroup per read: wave w sums the rows t = w (mod 4) of
-// each channel (coalesced 256-byte row segments, four rows in flight per channel group), LDS combines the four partial
-// sums in a fixed order, wave 0 finishes
-__global__ __launch_bounds__(256) void seq_head_kernel(const float* __restrict__ x, int T_pitch, int c,
-                                                       const float* __restrict__ fcw, const float* __restrict__ fcb,
-                                                       float* __restrict__ probs, float* __restrict__ logits,
-                                                       const int32_t* __restrict__ rt /* ragged batches: rows of read b (null: T_pitch) */) {
-    __shared__ float part[4][64];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int T = rt ? as_const_len(rt)[b] : T_pitch;
-    float a0 = 0.f, a1 = 0.f;
-    for (int c0 = 0; c0 < c; c0 += 64) {
-        const int ch = c0 + lane;
-        float s = 0.f;
-        if (ch < c) {
-            // eight rows in flight per lane (the loop is a chain of dependent-looking loads otherwise: T / 4 round trips)
-            const float* col = x + (int64_t)b * T_pitch * c + ch;
-            int t = wave;
-            for (; t + 28 < T; t += 32) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = col[(int64_t)(t + 4 * u) * c];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s += v[u];
-            }
-            for (; t < T; t += 4) s += col[(int64_t)t * c];
-        }
-        part[wave][lane] = s;
-        __syncthreads();
-        if (wave == 0 && ch < c) {
-            const float m = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / (float)T;
-            a0 = fmaf(m, fcw[ch], a0);
-            a1 = fmaf(m, fcw[c + ch], a1);
-        }
-        __syncthreads();
-    }
-    if (wave != 0) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a0 += __shfl_xor(a0, d, 64);
-        a1 += __shfl_xor(a1, d, 64);
-    }
-    if (lane == 0) {
-        const float l0 = a0 + fcb[0], l1 = a1 + fcb[1];
-        const float mx = fmaxf(l0, l1);
-        const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-        probs[2 * b] = e0 / (e0 + e1);
-        probs[2 * b + 1] = e1 / (e0 + e1);
-        if (logits) {
-            logits[2 * b] = l0;
-            logits[2 * b + 1] = l1;
-        }
-    }
 }
 
 // Ragged batches (rs_seqnet_forward_ragged): table[k + 1][b] = rows of read b after op k, table[0][b] = its samples.  One thread per

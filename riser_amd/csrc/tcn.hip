@@ -15,11 +15,13 @@
 //   - adds the 1x1 shortcut or the identity at the same strided rows, applies the ReLU, and writes only the rows the
 //     next block reads.
 // The GEMM M dimension is reads x positions: late blocks have a handful of positions per read and tile across reads.
-// tcn_head_kernel runs Linear(n_filters -> 2) + softmax on the one remaining position.  Every output element is a fixed
+// last_row_head_kernel (family/head.hpp) runs Linear(n_filters -> 2) + softmax on the one remaining position.  Every output element is a fixed
 // k-ordered fmaf chain whatever the tile, the batch or the row pitch: a read's result is that of the read alone, bit for bit.
 // rs_tcn_set_mode(m, RS_BF16X3) runs the blocks on csrc/tcn_x3.hip instead (split precision on the bf16 MFMA); the head and
 // the activation buffers are shared.
 #include "common.hpp"
+#include "family/head.hpp"
+#include "family/host.hpp"
 #include "tcn_x3.hpp"
 
 #include <algorithm>
@@ -34,11 +36,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxConvs = 4;
 constexpr int kLdsBudget = 64 * 1024;             // bytes of LDS per workgroup: two workgroups per CU
 constexpr int64_t kMaxDil = int64_t(1) << 40;      // dilations beyond any read length behave alike
-
-inline int cp4(int c) { return (c + 3) & ~3; }
-inline int np16(int c) { return (c + 15) & ~15; }
-// LDS row pitch: an odd number of float4 per row keeps the 16 rows x 4 k of an A fragment on distinct banks
-inline int lds_pitch(int cp) { return ((cp / 4) % 2 == 0) ? cp + 4 : cp; }
 
 struct BlockArgs {
     const float* x;             // block input: [B][in_rows][cp_in] (block 0: the signal, [B][ld])
@@ -176,34 +173,11 @@ __global__ __launch_bounds__(256) void tcn_block_kernel(const BlockArgs a) {
     }
 }
 
-// Linear(C -> 2) on the last position of every read + softmax (riser/model.py:27)
-__global__ __launch_bounds__(256) void tcn_head_kernel(const float* __restrict__ h, int B, int cp, int c, const float* __restrict__ fw,
-                                                       const float* __restrict__ fb, float* __restrict__ probs,
-                                                       float* __restrict__ logits) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const float* x = h + (int64_t)b * cp;
-    float l0 = fb[0], l1 = fb[1];
-    for (int i = 0; i < c; ++i) {
-        l0 = fmaf(fw[i], x[i], l0);
-        l1 = fmaf(fw[c + i], x[i], l1);
-    }
-    const float mx = fmaxf(l0, l1);
-    const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-    const float s = e0 + e1;
-    probs[2 * b] = e0 / s;
-    probs[2 * b + 1] = e1 / s;
-    if (logits) {
-        logits[2 * b] = l0;
-        logits[2 * b + 1] = l1;
-    }
-}
-
 struct ConvDev {
     int c_in = 0, c_out = 0, cpi = 0, cpo = 0, np = 0, k = 0;
-    float* w = nullptr;         // [k][cpi][np]: element (tap t reads m + t, ci, co) = w_ref[co][ci][k - 1 - t]
-    float* b = nullptr;         // [np]
-    unsigned short* xw = nullptr;   // RS_BF16X3: tcn_x3_pack planes
+    DevBuf<float> w;            // [k][cpi][np]: element (tap t reads m + t, ci, co) = w_ref[co][ci][k - 1 - t]
+    DevBuf<float> b;            // [np]
+    DevBuf<unsigned short> xw;  // RS_BF16X3: tcn_x3_pack planes
     int xsteps = 0;
 };
 
@@ -211,19 +185,12 @@ struct BlockDev {
     int nconv = 0, base = 1, jk = 0, c_in = 0, c_out = 0;
     int64_t dil = 1;
     ConvDev conv[kMaxConvs];
-    float* sw = nullptr;        // [cp_in][np_out]
-    float* sb = nullptr;
-    unsigned short* xsw = nullptr;  // RS_BF16X3: the shortcut's tcn_x3_pack planes
+    DevBuf<float> sw;           // [cp_in][np_out]; null: identity
+    DevBuf<float> sb;
+    DevBuf<unsigned short> xsw; // RS_BF16X3: the shortcut's tcn_x3_pack planes
     int xsw_steps = 0;
     int span = 0;               // sum of (k - 1) over the block's causal convs
 };
-
-template <class T>
-hipError_t upload(T** dst, const std::vector<T>& v) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T));
-    if (e == hipSuccess) e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
 
 }  // namespace
 }  // namespace rs
@@ -231,8 +198,7 @@ hipError_t upload(T** dst, const std::vector<T>& v) {
 struct rs_tcn {
     int device = 0;
     std::vector<rs::BlockDev> blocks;
-    float* d_fcw = nullptr;
-    float* d_fcb = nullptr;
+    rs::DevBuf<float> d_fcw, d_fcb;
     int c_last = 0;
     int64_t rf = 1;
     int mode = 0;               // rs_tcn_set_mode: 0 fp32 (f32-input MFMA), 1 split precision on the bf16 MFMA
@@ -323,8 +289,6 @@ size_t buffer_bytes(const rs_tcn* m, int64_t B, int ld) {
 
 // a * b for a, b >= 0, saturated at INT64_MAX
 int64_t sat_mul(int64_t a, int64_t b) { return (a != 0 && b > INT64_MAX / a) ? INT64_MAX : a * b; }
-
-constexpr int64_t kWindow = (int64_t(1) << 31) - 4096;     // every activation buffer stays inside 2 GiB
 
 // block i of an RS_BF16X3 forward (csrc/tcn_x3.hip): the tile choice of the fp32 path on the split LDS layout
 int launch_block_x3(const BlockDev& bd, int i, const float* in, const int32_t* d_len, float* out, int B, int ld, int in_rows,
@@ -456,7 +420,7 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
             const rs_tcn_conv& c = s.convs[j];
             ConvDev& cd = bd.conv[j];
             cd.c_in = c.c_in; cd.c_out = c.c_out; cd.k = c.k;
-            cd.cpi = cp4(c.c_in); cd.cpo = cp4(c.c_out); cd.np = np16(c.c_out);
+            cd.cpi = cp4(c.c_in); cd.cpo = cp4(c.c_out); cd.np = p16(c.c_out);
             std::vector<float> w((size_t)c.k * cd.cpi * cd.np, 0.0f), b(cd.np, 0.0f);
             for (int co = 0; co < c.c_out; ++co) {
                 b[co] = c.b[co];
@@ -464,10 +428,10 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
                     for (int t = 0; t < c.k; ++t)
                         w[((size_t)t * cd.cpi + ci) * cd.np + co] = c.w[((size_t)co * c.c_in + ci) * c.k + (c.k - 1 - t)];
             }
-            e = upload(&cd.w, w);
-            if (e == hipSuccess) e = upload(&cd.b, b);
+            e = upload(cd.w, w);
+            if (e == hipSuccess) e = upload(cd.b, b);
             int xnp = 0;
-            if (e == hipSuccess) e = upload(&cd.xw, tcn_x3_pack(c.w, c.c_out, c.c_in, c.k, &cd.xsteps, &xnp));
+            if (e == hipSuccess) e = upload(cd.xw, tcn_x3_pack(c.w, c.c_out, c.c_in, c.k, &cd.xsteps, &xnp));
             if (c.k > 1) {
                 bd.span += c.k - 1;
                 const int64_t add = sat_mul(c.k - 1, rf_dil);
@@ -475,18 +439,18 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
             }
         }
         if (e == hipSuccess && s.has_shortcut) {
-            const int cpi = cp4(bd.c_in), np = np16(bd.c_out);
+            const int cpi = cp4(bd.c_in), np = p16(bd.c_out);
             std::vector<float> w((size_t)cpi * np, 0.0f), b(np, 0.0f);
             for (int co = 0; co < bd.c_out; ++co) {
                 b[co] = s.sc_b[co];
                 for (int ci = 0; ci < bd.c_in; ++ci) w[(size_t)ci * np + co] = s.sc_w[(size_t)co * bd.c_in + ci];
             }
-            e = upload(&bd.sw, w);
-            if (e == hipSuccess) e = upload(&bd.sb, b);
+            e = upload(bd.sw, w);
+            if (e == hipSuccess) e = upload(bd.sb, b);
             int xnp = 0;
-            if (e == hipSuccess) e = upload(&bd.xsw, tcn_x3_pack(s.sc_w, bd.c_out, bd.c_in, 1, &bd.xsw_steps, &xnp));
+            if (e == hipSuccess) e = upload(bd.xsw, tcn_x3_pack(s.sc_w, bd.c_out, bd.c_in, 1, &bd.xsw_steps, &xnp));
         }
-        m->blocks.push_back(bd);
+        m->blocks.push_back(std::move(bd));
         dil = std::min<int64_t>(kMaxDil, dil * s.base);
         rf_dil = sat_mul(rf_dil, s.base);
     }
@@ -496,8 +460,8 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
         return RS_ERR_ARG;
     }
     m->rf = rf;
-    if (e == hipSuccess) e = upload(&m->d_fcw, std::vector<float>(fc_w, fc_w + 2 * (size_t)c_last));
-    if (e == hipSuccess) e = upload(&m->d_fcb, std::vector<float>(fc_b, fc_b + 2));
+    if (e == hipSuccess) e = upload(m->d_fcw, std::vector<float>(fc_w, fc_w + 2 * (size_t)c_last));
+    if (e == hipSuccess) e = upload(m->d_fcb, std::vector<float>(fc_b, fc_b + 2));
     if (e != hipSuccess) {
         rs_tcn_destroy(m);
         return hip_fail(e, "rs_tcn_create upload");
@@ -509,19 +473,7 @@ int rs_tcn_create(const rs_tcn_block* blocks, int n_blocks, const float* fc_w, c
 int rs_tcn_destroy(rs_tcn* m) {
     if (!m) return RS_OK;
     DeviceGuard guard(m->device);
-    for (BlockDev& b : m->blocks) {
-        for (int j = 0; j < kMaxConvs; ++j) {
-            if (b.conv[j].w) (void)hipFree(b.conv[j].w);
-            if (b.conv[j].b) (void)hipFree(b.conv[j].b);
-            if (b.conv[j].xw) (void)hipFree(b.conv[j].xw);
-        }
-        if (b.sw) (void)hipFree(b.sw);
-        if (b.sb) (void)hipFree(b.sb);
-        if (b.xsw) (void)hipFree(b.xsw);
-    }
-    if (m->d_fcw) (void)hipFree(m->d_fcw);
-    if (m->d_fcb) (void)hipFree(m->d_fcb);
-    delete m;
+    delete m;                           // every device buffer is a DevBuf: freed with its holder
     return RS_OK;
 }
 
@@ -571,40 +523,32 @@ size_t rs_tcn_workspace_bytes(const rs_tcn* m, int B, int ld) {
 
 int rs_tcn_max_batch(const rs_tcn* m, int ld) {
     if (!m || ld < 1) return 0;
-    const size_t per = buffer_bytes(m, 1, ld);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 30, kWindow / (int64_t)per));
+    return max_batch_of(buffer_bytes(m, 1, ld));
 }
 
 int rs_tcn_forward_ragged(rs_tcn* m, const float* d_x, const int32_t* d_len, int B, int ld, void* d_ws, size_t ws_bytes,
                           float* d_probs, float* d_logits, void* stream) {
-    if (!m || !d_x || !d_len || !d_ws || !d_probs || B < 1 || ld < 1) {
-        set_error("rs_tcn_forward_ragged: bad argument");
-        return RS_ERR_ARG;
-    }
-    if (ws_bytes < rs_tcn_workspace_bytes(m, B, ld)) {
-        set_error("rs_tcn_forward_ragged: workspace too small");
-        return RS_ERR_WORKSPACE;
-    }
-    const size_t per = buffer_bytes(m, B, ld);
-    if ((int64_t)per > kWindow) {
-        set_error("rs_tcn_forward_ragged: %d reads of %d samples outgrow the 2 GiB buffer window: split the batch "
-                  "(rs_tcn_max_batch)", B, ld);
-        return RS_ERR_ARG;
-    }
+    size_t per = 0;                     // one of the two buffers, B reads
+    const int rc = check_ragged_call("rs_tcn_forward_ragged", "rs_tcn_max_batch", m, d_x, d_len, d_ws, d_probs, B, ld, ws_bytes, [&] {
+        per = buffer_bytes(m, B, ld);
+        return RaggedLimits{1, 2 * per, (int64_t)per <= kWindow};
+    });
+    if (rc != RS_OK) return rc;
     DeviceGuard guard(m->device);
     RS_HIP(guard.err);
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::vector<int64_t> need;
     tcn_windows(m, ld, need);
-    float* buf[2] = {static_cast<float*>(d_ws), reinterpret_cast<float*>(static_cast<char*>(d_ws) + per)};
+    Carver ws(d_ws);
+    float* buf[2] = {ws.take(per), ws.take(per)};
     const float* in = d_x;
     const int n = (int)m->blocks.size();
     for (int i = 0; i < n; ++i) {
         const BlockDev& bd = m->blocks[i];
         const int out_rows = (int)need[i + 1];
         if (m->mode == 1) {
-            const int rc = launch_block_x3(bd, i, in, d_len, buf[i & 1], B, ld, (int)need[i], out_rows, st);
-            if (rc != RS_OK) return rc;
+            const int rcx = launch_block_x3(bd, i, in, d_len, buf[i & 1], B, ld, (int)need[i], out_rows, st);
+            if (rcx != RS_OK) return rcx;
             in = buf[i & 1];
             continue;
         }
@@ -664,8 +608,8 @@ int rs_tcn_forward_ragged(rs_tcn* m, const float* d_x, const int32_t* d_len, int
         RS_HIP(hipGetLastError());
         in = a.y;
     }
-    hipLaunchKernelGGL(tcn_head_kernel, dim3((B + 255) / 256), dim3(256), 0, st, in, B, cp4(m->c_last), m->c_last, m->d_fcw,
-                       m->d_fcb, d_probs, d_logits);
+    hipLaunchKernelGGL(last_row_head_kernel<AlwaysValid>, dim3((B + 255) / 256), dim3(256), 0, st, in, B, cp4(m->c_last), m->c_last,
+                       m->d_fcw, m->d_fcb, AlwaysValid{}, d_probs, d_logits);
     RS_HIP(hipGetLastError());
     return RS_OK;
 }

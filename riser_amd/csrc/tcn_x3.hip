@@ -15,7 +15,7 @@
 //     32 s + 8 kq .. + 7, all of one tap.  K indices behind the last tap read nothing (zero fragment) and meet zero weights.
 //   * The weights are split on the host (tcn_x3_pack) and read from global memory (L2) as 16-byte fragments:
 //     [hi | lo][step][kq][n][8], so a 16-lane group reads 256 contiguous bytes.
-//   * Bias, ReLU, the residual add and the block outputs stay fp32 (HBM layout [read][m][cp4], as in fp32: tcn_head_kernel is
+//   * Bias, ReLU, the residual add and the block outputs stay fp32 (HBM layout [read][m][cp4], as in fp32: the head kernel is
 //     reused unchanged).  The identity residual reads the fp32 block input from global memory, not its split form.
 //   * Block 0's first conv (1 input channel) and its 1 -> n shortcut run on the same path: K = k taps x 8 padded channels in one
 //     or two k-steps, a small share of block 0.

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as nv
+from ._family import FamilyNet
 
 
 def _np(sd):
@@ -107,25 +108,29 @@ def x3_layout(c_in: int, c_out: int, k: int, w=None):
     return out
 
 
-_MODES = {"f32": "f32", "f32w": "f32", "fp32": "f32", "bf16x3": "bf16x3"}
-
-
-class GConvNet:
+class GConvNet(FamilyNet):
     """A generic ConvNet on the device (rs_gconv_*): the surface Model drives for SeqNet - forward, forward_ragged,
     max_batch.  fp32 on the f32-input MFMA (the default) or, dtype 'bf16x3', the convs with more than 4 input channels in
-    split precision on the bf16 MFMA."""
+    split precision on the bf16 MFMA (rs_gconv_set_mode, also between forwards: fp32 after bf16x3 gives the bits of a fresh
+    fp32 net)."""
 
-    ragged_ok = True
+    _PREFIX = "rs_gconv"
+    _MODES = {"f32": ("f32", nv.RS_F32), "f32w": ("f32", nv.RS_F32W), "fp32": ("f32", nv.RS_F32),
+              "bf16x3": ("bf16x3", nv.RS_BF16X3)}
 
     def __init__(self, prog, device, dtype: str = "f32"):
-        self.dtype = "f32"
-        if _MODES.get(dtype) is None:
-            raise ValueError(f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic conv program "
-                             "in 'f32w' / 'f32' (f32-input MFMA) or 'bf16x3' (split precision on the bf16 MFMA) only")
-        nv.require_gpu()
-        d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
-        self._keep = prog
+        super().__init__(prog, device, dtype)
+
+    @classmethod
+    def _refused_dtype(cls, dtype):
+        return (f"dtype {dtype!r}: configs with depth > 1 or kernels other than 3 run the generic conv program in 'f32w' / "
+                "'f32' (f32-input MFMA) or 'bf16x3' (split precision on the bf16 MFMA) only")
+
+    def _no_workspace(self, B, ld):
+        return f"no workspace for {B} reads of {ld} samples (the network minimum is {self.min_length})"
+
+    def _create(self):
+        prog = self._keep
         convs = (_Conv * len(prog["convs"]))()
         for i, cv in enumerate(prog["convs"]):
             co, ci, k = cv["w"].shape
@@ -133,23 +138,7 @@ class GConvNet:
         h = C.c_void_p()
         nv.check(nv.lib().rs_gconv_create(convs, int(prog["n_layers"]), int(prog["depth"]), prog["fc_w"].ctypes.data,
                                           prog["fc_b"].ctypes.data, self.device.index, C.byref(h)), "rs_gconv_create")
-        self._h = h
-        self._ws = None
-        if _MODES[dtype] != "f32":
-            try:
-                self.set_mode(dtype)
-            except Exception:
-                self.close()
-                raise
-
-    def set_mode(self, dtype: str):
-        """'f32' / 'f32w' / 'fp32' or 'bf16x3' (rs_gconv_set_mode): the arithmetic of the next forward.  fp32 after bf16x3
-        gives the bits of a fresh fp32 net; a refused dtype leaves the mode as it was."""
-        mode = _MODES.get(dtype)
-        if mode is None:
-            raise ValueError(f"dtype {dtype!r}: a generic ConvNet runs in 'f32w' / 'f32' or 'bf16x3'")
-        nv.check(nv.lib().rs_gconv_set_mode(self._h, nv.RS_BF16X3 if mode == "bf16x3" else nv.RS_F32), "rs_gconv_set_mode")
-        self.dtype = mode
+        return h
 
     @property
     def min_length(self) -> int:
@@ -158,55 +147,3 @@ class GConvNet:
     def layer_plans(self):
         """layer_plan of every conv, in launch order"""
         return [layer_plan(cv["w"].shape[1], cv["w"].shape[0], cv["w"].shape[2]) for cv in self._keep["convs"]]
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            nv.lib().rs_gconv_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def max_batch(self, L: int) -> int:
-        """largest batch of reads of (pitch) L samples one call can address: both activation buffers inside the 2 GiB window
-        (rs_gconv_max_batch); forward_ragged splits bigger batches"""
-        return max(1, int(nv.lib().rs_gconv_max_batch(self._h, int(L))))
-
-    def forward(self, x: torch.Tensor, return_logits: bool = False):
-        """x: fp32 device tensor [B, L] (one common length) -> fp32 [B, 2] on the device."""
-        B, L = x.shape
-        lens = torch.full((B,), L, dtype=torch.int32, device=self.device)
-        return self.forward_ragged(x, lens, return_logits)
-
-    def forward_ragged(self, x: torch.Tensor, lens_dev: torch.Tensor, return_logits: bool = False, out: torch.Tensor = None):
-        """x: fp32 device tensor [B, ld], read b = x[b, :lens_dev[b]] (int32 on the device) -> fp32 [B, 2] on the device;
-        every read's result is that of forward() on it alone, bit for bit."""
-        B, ld = x.shape
-        if not x.is_contiguous():                   # the device reads row b at x + b * ld
-            raise ValueError("x must be contiguous: its row pitch is its second dimension")
-        lib = nv.lib()
-        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-        mb = self.max_batch(ld)
-        if B > mb:                                  # reads are independent: equal parts, each inside the buffer window
-            parts = -(-B // mb)
-            step = -(-B // parts)
-            for s0 in range(0, B, step):
-                s1 = min(B, s0 + step)
-                r = self.forward_ragged(x[s0:s1], lens_dev[s0:s1], return_logits, out=probs[s0:s1])
-                if return_logits:
-                    logits[s0:s1] = r[1]
-            return (probs, logits) if return_logits else probs
-        need = lib.rs_gconv_workspace_bytes(self._h, B, ld)
-        if need == 0:
-            raise ValueError(f"no workspace for {B} reads of {ld} samples (the network minimum is {self.min_length})")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        nv.check(lib.rs_gconv_forward_ragged(self._h, x.data_ptr(), lens_dev.data_ptr(), B, ld, self._ws.data_ptr(),
-                                             self._ws.numel(), probs.data_ptr(), logits.data_ptr() if return_logits else None,
-                                             torch.cuda.current_stream(self.device).cuda_stream), "rs_gconv_forward_ragged")
-        return (probs, logits) if return_logits else probs

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _native as nv
+from ._family import FamilyNet
 
 _BN_EPS = 1e-5
 
@@ -136,16 +137,28 @@ def program_traffic_bytes(prog, L: int, fused: bool = True) -> float:
     return 4.0 * total
 
 
-class SeqNet:
-    """A conv / max-pool program on the device (rs_seqnet_*): uniform-length batches [B, L] -> probabilities."""
+class SeqNet(FamilyNet):
+    """A conv / max-pool program on the device (rs_seqnet_*): uniform-length batches [B, L] -> probabilities, and ragged ones
+    where ragged_ok.  dtype: "f32" (every conv on the f32-input MFMA) or "bf16x3" (the stem and the residual blocks in split
+    precision on the bf16 MFMA, rs_seqnet_set_mode: within 1e-3 of the reference, ~1.6 x the fp32 rate)."""
+
+    _PREFIX = "rs_seqnet"
+    _MODES = {"f32": ("f32", nv.RS_F32), "f32w": ("f32", nv.RS_F32W), "fp32": ("f32", nv.RS_F32),
+              "bf16x3": ("bf16x3", nv.RS_BF16X3)}
 
     def __init__(self, prog, n_buffers, fw, fb, c_last, device, dtype: str = "f32"):
-        """dtype: "f32" (every conv on the f32-input MFMA) or "bf16x3" (the stem and the residual blocks in split precision on the
-        bf16 MFMA, rs_seqnet_set_mode: within 1e-3 of the reference, ~1.6 x the fp32 rate)."""
-        nv.require_gpu()
-        d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
-        self._keep = (prog, fw, fb)
+        self._n_buffers, self._c_last = n_buffers, c_last
+        super().__init__((prog, fw, fb), device, dtype)
+
+    @classmethod
+    def _refused_dtype(cls, dtype):
+        return f"dtype {dtype!r}: generic conv programs run in 'f32' or 'bf16x3'"
+
+    def _no_workspace(self, B, ld):
+        return f"a row pitch of {ld} samples is too short for this network"
+
+    def _create(self):
+        prog, fw, fb = self._keep
         ops = []
         for o in prog:
             if o["kind"] == 0:
@@ -156,52 +169,21 @@ class SeqNet:
                 ops.append(nv.SeqOp(1, o["src"], o["dst"], -1, 0, 0, 0, 0, int(o.get("pad", 1)), 0, None, None))
         arr = (nv.SeqOp * len(ops))(*ops)
         h = C.c_void_p()
-        nv.check(nv.lib().rs_seqnet_create(arr, len(ops), n_buffers, fw.ctypes.data, fb.ctypes.data, c_last,
+        nv.check(nv.lib().rs_seqnet_create(arr, len(ops), self._n_buffers, fw.ctypes.data, fb.ctypes.data, self._c_last,
                                            self.device.index, C.byref(h)), "rs_seqnet_create")
-        self._h = h
-        self._ws = None
-        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32", "bf16x3": "bf16x3"}.get(dtype)
-        if self.dtype is None:
-            self.close()
-            raise ValueError(f"dtype {dtype!r}: generic conv programs run in 'f32' or 'bf16x3'")
-        if self.dtype == "bf16x3":
-            try:
-                nv.check(nv.lib().rs_seqnet_set_mode(self._h, nv.RS_BF16X3), "rs_seqnet_set_mode")
-            except Exception:
-                self.close()
-                raise
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            nv.lib().rs_seqnet_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return h
 
     def forward(self, x: torch.Tensor, return_logits: bool = False):
-        """x: fp32 device tensor [B, L] (one common length) -> fp32 [B, 2] on the device."""
+        """x: fp32 device tensor [B, L] (one common length) -> fp32 [B, 2] on the device (rs_seqnet_forward: also the
+        programs that are not ragged_ok)."""
         B, L = x.shape
-        lib = nv.lib()
-        need = lib.rs_seqnet_workspace_bytes(self._h, B, L)
-        if need == 0:
-            raise ValueError(f"signal of {L} samples is too short for this network")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace(B, L, lambda B, L: f"signal of {L} samples is too short for this network")
         probs = torch.empty((B, 2), dtype=torch.float32, device=self.device)
         logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-        nv.check(lib.rs_seqnet_forward(self._h, x.data_ptr(), B, L, self._ws.data_ptr(), self._ws.numel(),
-                                       probs.data_ptr(), logits.data_ptr() if return_logits else None,
-                                       torch.cuda.current_stream(self.device).cuda_stream), "rs_seqnet_forward")
+        nv.check(nv.lib().rs_seqnet_forward(self._h, x.data_ptr(), B, L, ws.data_ptr(), ws.numel(),
+                                            probs.data_ptr(), logits.data_ptr() if return_logits else None,
+                                            torch.cuda.current_stream(self.device).cuda_stream), "rs_seqnet_forward")
         return (probs, logits) if return_logits else probs
-
-    def max_batch(self, L: int) -> int:
-        """largest batch of reads of (pitch) L samples one call can address: every activation buffer stays inside the kernels'
-        2 GiB buffer window (rs_seqnet_max_batch); bigger batches are split by the callers below and in riser_amd.Model"""
-        return max(1, int(nv.lib().rs_seqnet_max_batch(self._h, int(L))))
 
     def launch_plan(self, B: int, L: int, ragged: bool = False):
         """the launches a forward of B reads at length (ragged: row pitch) L makes in the current mode (rs_seqnet_launch_plan):
@@ -221,35 +203,6 @@ class SeqNet:
     def ragged_ok(self) -> bool:
         """True when forward_ragged can run this program (all of its ops inside fused launches: a ResNet's stem and blocks)"""
         return bool(nv.lib().rs_seqnet_ragged_ok(self._h))
-
-    def forward_ragged(self, x: torch.Tensor, lens_dev: torch.Tensor, return_logits: bool = False, out: torch.Tensor = None):
-        """x: fp32 device tensor [B, ld], read b = x[b, :lens_dev[b]] (int32 on the device) -> fp32 [B, 2] on the device; every
-        read's result is that of forward() on it alone."""
-        B, ld = x.shape
-        lib = nv.lib()
-        mb = self.max_batch(ld)
-        if B > mb:                                  # reads are independent: equal parts, each inside the buffer window
-            probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-            logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-            parts = -(-B // mb)
-            step = -(-B // parts)
-            for s0 in range(0, B, step):
-                s1 = min(B, s0 + step)
-                r = self.forward_ragged(x[s0:s1], lens_dev[s0:s1], return_logits, out=probs[s0:s1])
-                if return_logits:
-                    logits[s0:s1] = r[1]
-            return (probs, logits) if return_logits else probs
-        need = lib.rs_seqnet_workspace_bytes(self._h, B, ld)
-        if need == 0:
-            raise ValueError(f"a row pitch of {ld} samples is too short for this network")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-        nv.check(lib.rs_seqnet_forward_ragged(self._h, x.data_ptr(), lens_dev.data_ptr(), B, ld, self._ws.data_ptr(),
-                                              self._ws.numel(), probs.data_ptr(), logits.data_ptr() if return_logits else None,
-                                              torch.cuda.current_stream(self.device).cuda_stream), "rs_seqnet_forward_ragged")
-        return (probs, logits) if return_logits else probs
 
 
 def build_convnet_program(sd, cnn):

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as nv
+from ._family import FamilyNet
 
 
 def _fold_weight_norm(sd, prefix):
@@ -134,22 +135,25 @@ class _TcnBlock(C.Structure):
                 ("reserved", C.c_int32), ("sc_w", C.c_void_p), ("sc_b", C.c_void_p)]
 
 
-class TCNNet:
-    """A TCN / TCNBot on the device (rs_tcn_*): the surface Model drives for SeqNet - forward, forward_ragged, max_batch."""
+class TCNNet(FamilyNet):
+    """A TCN / TCNBot on the device (rs_tcn_*): the surface Model drives for SeqNet - forward, forward_ragged, max_batch.
+    dtype: 'f32' / 'f32w' / 'fp32' (fp32 on the f32-input MFMA) or 'bf16x3' (every conv in split precision on the bf16 MFMA,
+    csrc/tcn_x3.hip: rs_tcn_set_mode)"""
 
-    ragged_ok = True
+    _PREFIX = "rs_tcn"
+    _MODES = {"f32": ("f32", nv.RS_F32), "f32w": ("f32", nv.RS_F32W), "fp32": ("f32", nv.RS_F32),
+              "bf16x3": ("bf16x3", nv.RS_BF16X3)}
 
     def __init__(self, blocks, fw, fb, device, dtype: str = "f32"):
-        """dtype: 'f32' / 'f32w' / 'fp32' (fp32 on the f32-input MFMA) or 'bf16x3' (every conv in split precision on the
-        bf16 MFMA, csrc/tcn_x3.hip: rs_tcn_set_mode)"""
-        self.dtype = {"f32": "f32", "f32w": "f32", "fp32": "f32", "bf16x3": "bf16x3"}.get(dtype)
-        if self.dtype is None:
-            raise ValueError(f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (f32-input MFMA) or 'bf16x3' (split precision "
-                             "on the bf16 MFMA)")
-        nv.require_gpu()
-        d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
-        self._keep = (blocks, fw, fb)
+        super().__init__((blocks, fw, fb), device, dtype)
+
+    @classmethod
+    def _refused_dtype(cls, dtype):
+        return (f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (f32-input MFMA) or 'bf16x3' (split precision on the bf16 "
+                "MFMA)")
+
+    def _create(self):
+        blocks, fw, fb = self._keep
         arr = (_TcnBlock * len(blocks))()
         for i, b in enumerate(blocks):
             arr[i].n_convs = len(b["convs"])
@@ -164,60 +168,8 @@ class TCNNet:
         h = C.c_void_p()
         nv.check(nv.lib().rs_tcn_create(arr, len(blocks), fw.ctypes.data, fb.ctypes.data, int(fw.shape[1]),
                                         self.device.index, C.byref(h)), "rs_tcn_create")
-        self._h = h
-        self._ws = None
-        if self.dtype == "bf16x3":
-            nv.check(nv.lib().rs_tcn_set_mode(h, nv.RS_BF16X3), "rs_tcn_set_mode")
+        return h
 
     @property
     def receptive_field(self) -> int:
         return int(nv.lib().rs_tcn_receptive_field(self._h))
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            nv.lib().rs_tcn_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def max_batch(self, L: int) -> int:
-        """largest batch of reads of (pitch) L samples one call can address: every activation buffer inside the 2 GiB
-        window (rs_tcn_max_batch); forward_ragged splits bigger batches"""
-        return max(1, int(nv.lib().rs_tcn_max_batch(self._h, int(L))))
-
-    def forward(self, x: torch.Tensor, return_logits: bool = False):
-        """x: fp32 device tensor [B, L] (one common length) -> fp32 [B, 2] on the device."""
-        B, L = x.shape
-        lens = torch.full((B,), L, dtype=torch.int32, device=self.device)
-        return self.forward_ragged(x, lens, return_logits)
-
-    def forward_ragged(self, x: torch.Tensor, lens_dev: torch.Tensor, return_logits: bool = False, out: torch.Tensor = None):
-        """x: fp32 device tensor [B, ld], read b = x[b, :lens_dev[b]] (int32 on the device) -> fp32 [B, 2] on the device;
-        every read's result is that of forward() on it alone, bit for bit."""
-        B, ld = x.shape
-        lib = nv.lib()
-        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-        mb = self.max_batch(ld)
-        if B > mb:                                  # reads are independent: equal parts, each inside the buffer window
-            parts = -(-B // mb)
-            step = -(-B // parts)
-            for s0 in range(0, B, step):
-                s1 = min(B, s0 + step)
-                r = self.forward_ragged(x[s0:s1], lens_dev[s0:s1], return_logits, out=probs[s0:s1])
-                if return_logits:
-                    logits[s0:s1] = r[1]
-            return (probs, logits) if return_logits else probs
-        need = lib.rs_tcn_workspace_bytes(self._h, B, ld)
-        if need == 0:
-            raise ValueError(f"no workspace for {B} reads of {ld} samples")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        nv.check(lib.rs_tcn_forward_ragged(self._h, x.data_ptr(), lens_dev.data_ptr(), B, ld, self._ws.data_ptr(),
-                                           self._ws.numel(), probs.data_ptr(), logits.data_ptr() if return_logits else None,
-                                           torch.cuda.current_stream(self.device).cuda_stream), "rs_tcn_forward_ragged")
-        return (probs, logits) if return_logits else probs

@@ -474,7 +474,7 @@ def test_tile_forms(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", NAMES)
 def test_length_clamp(name):
-    """crnn_len clamps a length to [0, ld]; a read too short for the net gets NaN from crnn_head_kernel and disturbs nobody.
+    """crnn_len clamps a length to [0, ld]; a read too short for the net gets NaN from last_row_head_kernel (family/head.hpp) and disturbs nobody.
     Defined behaviour of the device program (Model refuses such batches first, so this goes through CRNNNet)."""
     m = _model(name)
     net = m._seq
