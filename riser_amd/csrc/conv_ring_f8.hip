@@ -29,6 +29,7 @@
 // activation slab's first half.  IN_F8 = false reads split-precision rows ([hi x 32 | lo x 32] f16, three MFMAs: the first
 // layer of a run), OUT_F8 = false writes them (the last layer: the head reads hi + lo).
 #include "common.hpp"
+#include "conv_h16_device.hpp"
 #include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
@@ -57,17 +58,11 @@
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kThreads = 512;
 constexpr int kRowB = 128;                      // bytes of an LDS row (one panel)
 constexpr int kPieceRows = 1024 / kRowB;        // rows per DMA piece (one wave instruction)
-constexpr unsigned kOob = 0x80000000u;
 // E8M0 bytes of the weight planes (convnet_pack.hpp: F8Layout packs hi8 = e4m3(hi 2^-6), lo8 = e4m3(lo 2^5))
 constexpr int kWScaleHi = 127 + 6, kWScaleLo = 127 - 5;
 
@@ -97,11 +92,12 @@ struct F8Args {
     unsigned long long* stamps;  // diagnostic builds only
 };
 
-__device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f32x4& c) {
+// the 16-bit half of this mode is f16: conv_h16_device.hpp's <true> instantiations (mfma16, pack2, widen16)
+__device__ __forceinline__ f32x4 mfma16h(const u32x4& a, const u32x4& b, const f32x4& c) {
 #ifdef RS_F8_NO_H                // diagnostic build: no 16-bit MFMAs
     return c;
 #endif
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    return mfma16<true>(a, b, c);
 }
 // unit k of A (32 e4m3 values of one row) against unit k of B, k = 0..3, each scaled by its lane's E8M0 byte
 __device__ __forceinline__ f32x4 mfma8(const u32x4& a_lo, const u32x4& a_hi, const u32x4& b_lo, const u32x4& b_hi, int sa, int sb,
@@ -114,7 +110,8 @@ __device__ __forceinline__ f32x4 mfma8(const u32x4& a_lo, const u32x4& a_hi, con
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, c, 0, 0, 0, sa, 0, sb);
 }
 
-// one LDS-DMA piece: lane l's 16 bytes at rsrc + voff land at LDS byte lds_addr + 16 l (zeros if voff is out of range)
+// one LDS-DMA piece, as conv_h16_device.hpp's, but on a descriptor of four plain dwords (make_desc): this kernel runs short of
+// scalar registers, where the opaque descriptor type of the shared form is handed to the inline asm in vector registers
 // (TAG keeps the compiler from merging the two arms of a wave-uniform branch over different descriptors into ONE instruction
 // with a selected - vector-register - descriptor)
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -137,32 +134,11 @@ __device__ __forceinline__ void dma_piece(unsigned voff, const i32x4 rsrc_, unsi
                      :: "v"(voff), "s"(m0v), "s"(rsrc) : "memory");
 }
 
-// two fp32 -> one dword of two f16 (lo in bits 0-15), round to nearest even
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-}
-__device__ __forceinline__ float widen16(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
-
-// value of the lane that holds the neighbouring output column (lane ^ 1)
-__device__ __forceinline__ float swap_pair(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1 /* quad_perm [1,0,3,2] */,
-                                                              0xF, 0xF, true));
-}
 // packed f16 maximum with the lane `ctrl` points at (all 16 lanes of a row take part)
 template <int CTRL>
 __device__ __forceinline__ unsigned pkmax_dpp(unsigned v) {
     const unsigned o = (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(f16x2, v), __builtin_bit_cast(f16x2, o)));
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
 }
 
 // kinds of K panel
@@ -364,7 +340,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_f8_kernel(const F8Args 
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = mfma16(keep_a[i], keep_b[j], acc[i][j]);
+                for (int j = 0; j < NT; ++j) acc[i][j] = mfma16h(keep_a[i], keep_b[j], acc[i][j]);
         }
     };
     auto substage = [&](auto KIND_, auto PREV_, auto TAP, int xb, bool have_prev, auto NDMA_, auto&& dma, auto&& between) __attribute__((always_inline)) {
@@ -400,9 +376,9 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_f8_kernel(const F8Args 
             } else {
                 constexpr int pass = n / (MT * NT), ij = n % (MT * NT), i = ij / NT, j = ij % NT;
                 if constexpr (pass == 0)
-                    acc[i][j] = mfma16(a0[i], b0[j], acc[i][j]);           // x3: hi * hi;  H: h0 * h0
+                    acc[i][j] = mfma16h(a0[i], b0[j], acc[i][j]);           // x3: hi * hi;  H: h0 * h0
                 else
-                    acc[i][j] = mfma16(a1[i], b0[j], acc[i][j]);           // x3: lo * hi
+                    acc[i][j] = mfma16h(a1[i], b0[j], acc[i][j]);           // x3: lo * hi
             }
             if constexpr (NDMA > 0 && n % GAP == GAP - 1 && n / GAP < NDMA) dma(std::integral_constant<int, n / GAP>{});
         });
@@ -478,7 +454,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_f8_kernel(const F8Args 
                 const float got = swap_pair(odd ? v0 : v1);
                 ca[j] = odd ? got : v0;
                 cb_[j] = odd ? v1 : got;
-                hi[j] = pack2(ca[j], cb_[j]) & keep;
+                hi[j] = pack2<true>(ca[j], cb_[j]) & keep;
                 sat |= f16_overflow_bits(hi[j]);
                 acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
@@ -499,7 +475,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_f8_kernel(const F8Args 
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {
                         const int j = 2 * u + jj;
-                        const float h0 = widen16((unsigned short)(hi[j] & 0xffffu)), h1 = widen16((unsigned short)(hi[j] >> 16));
+                        const float h0 = widen16<true>((unsigned short)(hi[j] & 0xffffu)), h1 = widen16<true>((unsigned short)(hi[j] >> 16));
                         const unsigned q8 = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(h0 * mul_hi, h1 * mul_hi, 0, false) & 0xffffu;
                         const unsigned l8 = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32((ca[j] - h0) * mul_lo, (cb_[j] - h1) * mul_lo, 0, false) & keep & 0xffffu;
                         unsigned char* dst = scr + (2 * g + (odd ? 1 : 0)) * PITCH + j * PW * 16;
@@ -518,8 +494,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_f8_kernel(const F8Args 
                 for (int j = 0; j < NT; ++j) {
                     unsigned char* dst = scr + (2 * g + (odd ? 1 : 0)) * PITCH + j * PW * 16 + (r & ~1) * 2;
                     *reinterpret_cast<unsigned*>(dst) = hi[j];
-                    *reinterpret_cast<unsigned*>(dst + 32) = keep &
-                        pack2(ca[j] - widen16((unsigned short)(hi[j] & 0xffffu)), cb_[j] - widen16((unsigned short)(hi[j] >> 16)));
+                    *reinterpret_cast<unsigned*>(dst + 32) = keep & pack2_lo<true>(ca[j], cb_[j], hi[j]);
                 }
             }
 #pragma unroll

@@ -25,6 +25,7 @@
 // The accumulation order over K is panel -> tap -> half, identical to the round-1 kernel with 64-channel panels: plain-mode
 // results are bit-identical to that kernel.
 #include "common.hpp"
+#include "conv_h16_device.hpp"
 #include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
@@ -54,15 +55,9 @@
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kThreads = 512;
 constexpr int kRowB = 128;                      // bytes of an LDS row (one panel)
 constexpr int kPieceRows = 1024 / kRowB;        // rows per DMA piece (one wave instruction)
-constexpr unsigned kOob = 0x80000000u;
 
 struct RingArgs {
     const unsigned short* x;     // [rows_in][cpx_in]
@@ -88,78 +83,6 @@ struct RingArgs {
     WalkArgs walk;
     unsigned long long* stamps;  // diagnostic builds only
 };
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
-                                                      0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
-}
-
-template <bool F16>
-__device__ __forceinline__ unsigned short cvt16(float f) {
-    if constexpr (F16)
-        return __builtin_bit_cast(unsigned short, (_Float16)f);
-    else
-        return __builtin_bit_cast(unsigned short, (__bf16)f);
-}
-template <bool F16>
-__device__ __forceinline__ float widen16(unsigned short u) {
-    if constexpr (F16)
-        return (float)__builtin_bit_cast(_Float16, u);
-    else
-        return __builtin_bit_cast(float, (unsigned)u << 16);
-}
-
-// one LDS-DMA piece: lane l's 16 bytes at rsrc + voff land at LDS byte lds_addr + 16 l (zeros if voff is out of range)
-__device__ __forceinline__ void dma_piece(unsigned voff, const __amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr) {
-    // the LDS address is wave-uniform by construction; readfirstlane makes that provable to the compiler ("s" operand)
-    const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(m0v), "s"(rsrc) : "memory");
-#if defined(RS_EMU_DMA_X) && RS_EMU_DMA_X == 2       // measurement build: every staging piece issued twice (2 x the L2 -> LDS bytes)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(m0v), "s"(rsrc) : "memory");
-#endif
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// two fp32 -> one dword of two 16-bit values (lo in bits 0-15), round to nearest even (v_cvt_pk_{f16,bf16}_f32)
-template <bool F16>
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    if constexpr (F16)
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-    else
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-// value of the lane that holds the neighbouring output column (lane ^ 1)
-__device__ __forceinline__ float swap_pair(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1 /* quad_perm [1,0,3,2] */,
-                                                              0xF, 0xF, true));
-}
-
-// physical element index of logical output column c inside a row
-template <bool X3>
-__device__ __forceinline__ int phys_col(int c) {
-    return X3 ? ((c >> 5) << 6) + (c & 31) : c;
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
 
 template <int WM, int WN, int MT, int NT, bool F16, bool X3, bool TAIL = false>
 __global__ __launch_bounds__(kThreads, 2) void conv_ring_h16_kernel(const RingArgs a) {
@@ -497,9 +420,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_h16_kernel(const RingAr
     // an out-of-range offset).  The scratch aliases the activation slab the tile has just finished with; the barrier
     // behind the epilogue keeps the next sub-stage's pieces out of it.  LDS operations of one wave execute in order,
     // so the image needs no wait between its writes and its reads.
-    constexpr int PW = X3 ? 4 : 2;                                  // 16-byte pieces per 16-channel group of an output row
-    constexpr int PITCH = NT * PW * 16 + 16;                        // scratch row pitch: rows 2g of the 4 lane groups on distinct banks
-    constexpr int NPIECE = 8 * NT * PW;                             // pieces of one block's 8 pooled rows
+    using Epi = EpiImage<NT, X3>;
+    constexpr int PW = Epi::PW, PITCH = Epi::PITCH, NPIECE = Epi::NPIECE;
     // free at this point: the tile's last activation slab and the tap-2 weight slab (the next panel's is issued after
     // the barrier); short tiles put waves 4-7 into the latter
     constexpr bool SCR_IN_X = 8 * (8 * PITCH) <= XS;
@@ -531,20 +453,10 @@ __global__ __launch_bounds__(kThreads, 2) void conv_ring_h16_kernel(const RingAr
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                // MaxPool, + bias, ReLU: max(a, b) + c == max(a + c, b + c) bit for bit (rounding is monotonic); the sums
-                // are canonical, so the compiler emits one v_max3_f32 instead of two canonicalising v_max + max + max
-                const float us = a.unscale;                  // fmaf(x, 1, b) == x + b bit for bit: nothing changes outside f16
-                const float v0 = fmaxf(fmaxf(fmaf(acc[i][j][0], us, bias[j]), fmaf(acc[i][j][1], us, bias[j])), 0.0f);
-                const float v1 = fmaxf(fmaxf(fmaf(acc[i][j][2], us, bias[j]), fmaf(acc[i][j][3], us, bias[j])), 0.0f);
-                const float got = swap_pair(odd ? v0 : v1);
-                const float ca = odd ? got : v0, cb_ = odd ? v1 : got;          // channels (r & ~1, r | 1) of row 2g + odd
-                const unsigned hi = pack2<F16>(ca, cb_);
-                if constexpr (F16) sat |= f16_overflow_bits(hi);
+                const u32x2 hl = pool_pack_pair<F16, X3>(acc[i][j], a.unscale, bias[j], odd, keep, sat);
                 unsigned char* dst = scr + (2 * g + (odd ? 1 : 0)) * PITCH + j * PW * 16 + (r & ~1) * 2;
-                *reinterpret_cast<unsigned*>(dst) = hi & keep;
-                if constexpr (X3)
-                    *reinterpret_cast<unsigned*>(dst + 32) = keep &
-                        pack2<F16>(ca - widen16<F16>((unsigned short)(hi & 0xffffu)), cb_ - widen16<F16>((unsigned short)(hi >> 16)));
+                *reinterpret_cast<unsigned*>(dst) = hl[0];
+                if constexpr (X3) *reinterpret_cast<unsigned*>(dst + 32) = hl[1];
                 acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll

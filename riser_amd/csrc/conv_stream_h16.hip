@@ -34,6 +34,7 @@
 // come from the ring packing [tap][n_alloc][hi x 32 | lo x 32], a product is three MFMAs (hi*hi, lo*hi, hi*lo) and
 // the epilogue splits every output once more.  Twice the weight registers: two waves per SIMD instead of four.
 #include "common.hpp"
+#include "conv_h16_device.hpp"
 
 #include <stdlib.h>
 
@@ -44,27 +45,11 @@
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 #ifndef RS_STREAM_WGS
 #define RS_STREAM_WGS 4
 #endif
 constexpr int kWaves = 4;                     // per workgroup; each wave is independent
 constexpr int kRing = 64;                     // ring rows per wave (64 bytes each): 4 sub-tiles, 3 are live
-constexpr unsigned kOob = 0x80000000u;
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
 
 struct StreamArgs {
     const void* x;            // producer = load: 16-bit activations [rows_in][cp_in]; FUSE0: unused
@@ -88,52 +73,206 @@ struct StreamArgs {
     int sub_per_wave;
 };
 
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
-                                                      0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                       c, 0, 0, 0);
+// ======================================================================================================
+// The wave-private pipeline both kernels below are made of: layer-0 sub-tile -> park -> conv block -> row store.
+// ROWP, the ring row pitch: 16 bytes more than a row (64 bytes, X3: 128), so that the consumer's ds_read_b128 of every SECOND
+// row (rows 2c + d of lane group c) and the producer's ds_write_b128 of consecutive rows are both free of bank conflicts
+// without a swizzle (slot = (5 row + kq) mod 16 resp. (9 row + kq) mod 16 over the 16-lane groups of ds_read_b128)
+template <bool X3>
+constexpr int kRowP = (X3 ? 128 : 64) + 16;
+// channel tiles a block hands on per row: X3 rows hold 32 channel slots per panel, so the NT computed tiles are filled up to pairs
+template <int NT, bool X3>
+constexpr int kStoreTiles = X3 ? 2 * ((NT + 1) / 2) : NT;
+
+struct SubInfo {
+    int t0, l0;                                                 // first row's position in its read; valid rows of the read
+};
+template <bool X3>
+struct Row {
+    u32x4 v[X3 ? 2 : 1];                                        // this lane's 8 channels of its row: hi (and lo)
+};
+
+// Layer 0 of 16 pooled rows on the matrix pipe (v_mfma_f32_16x16x4_f32, K = 3 taps + one zero column; bit-exact fmaf chains
+// from the accumulator input, which carries the bias: the same chain as conv0_kernel): A = w0t[m] = W0[channel 16m + r][tap kq],
+// C = cb[m] = bias of channels 16m + 4kq + i, B = (xe, xo) = x[2g - 1 + kq], x[2g + kq] of this lane.  Columns = pooled rows,
+// one MFMA for their even conv positions and one for the odd ones per 16-channel tile, so MaxPool + ReLU is one v_max3_f32 per
+// value, in-lane.  The lane then holds channels 4kq .. +3 and 16 + 4kq .. +3 of its row; v_permlane16_swap_b32 turns that into
+// 8 consecutive channels (16 (kq & 1) + 8 (kq >> 1) ..), which is a 16-byte slot of the ring row in natural order.
+template <bool F16, bool X3>
+__device__ __forceinline__ Row<X3> conv0_subtile(unsigned ue, unsigned uo, const float (&w0t)[2], const f32x4 (&cb)[2], unsigned& sat) {
+    constexpr int NH = X3 ? 2 : 1;
+    const float xe = __builtin_bit_cast(float, ue), xo = __builtin_bit_cast(float, uo);
+    float o[2][4];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+#ifdef RS_ABL_NOCONV0
+        const f32x4 e = cb[m] * xe, f = cb[m] * xo;
+#else
+        const f32x4 e = __builtin_amdgcn_mfma_f32_16x16x4f32(w0t[m], xe, cb[m], 0, 0, 0);
+        const f32x4 f = __builtin_amdgcn_mfma_f32_16x16x4f32(w0t[m], xo, cb[m], 0, 0, 0);
+#endif
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[m][i] = fmaxf(fmaxf(e[i], f[i]), 0.0f);
+    }
+    unsigned w[NH][2][2];                                       // [hi / lo][tile][dword]
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        w[0][m][0] = pack2<F16>(o[m][0], o[m][1]);
+        w[0][m][1] = pack2<F16>(o[m][2], o[m][3]);
+        if constexpr (F16) sat |= f16_overflow_bits(w[0][m][0]) | f16_overflow_bits(w[0][m][1]);
+        if constexpr (X3) {
+            w[1][m][0] = pack2_lo<F16>(o[m][0], o[m][1], w[0][m][0]);
+            w[1][m][1] = pack2_lo<F16>(o[m][2], o[m][3], w[0][m][1]);
+        }
+    }
+    Row<X3> out;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const auto s0 = __builtin_amdgcn_permlane16_swap(w[h][0][0], w[h][1][0], false, false);
+        const auto s1 = __builtin_amdgcn_permlane16_swap(w[h][0][1], w[h][1][1], false, false);
+        out.v[h] = (u32x4){s0[0], s1[0], s0[1], s1[1]};
+    }
+    return out;
+}
+// ... of a sub-tile at a read's end: rows beyond the read's length are zero rows; a sub-tile wholly beyond it costs no arithmetic
+template <bool F16, bool X3>
+__device__ __forceinline__ Row<X3> conv0_subtile_masked(unsigned ue, unsigned uo, const float (&w0t)[2], const f32x4 (&cb)[2], unsigned& sat,
+                                                        int r, const SubInfo& si) {
+    constexpr int NH = X3 ? 2 : 1;
+    Row<X3> v;
+    if (si.t0 >= si.l0) {
+#pragma unroll
+        for (int h = 0; h < NH; ++h) v.v[h] = (u32x4){0u, 0u, 0u, 0u};
+    } else {
+        v = conv0_subtile<F16, X3>(ue, uo, w0t, cb, sat);
+        const unsigned keep = si.t0 + r < si.l0 ? ~0u : 0u;
+#pragma unroll
+        for (int h = 0; h < NH; ++h) v.v[h] &= (u32x4){keep, keep, keep, keep};
+    }
+    return v;
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// two fp32 -> one dword of two 16-bit values, round to nearest even (v_cvt_pk_{f16,bf16}_f32)
-template <bool F16>
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    if constexpr (F16)
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-    else
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+// sub-tile u occupies ring rows 16 (u & 3) ..; ring_w = this lane's byte in ring row 0 of a sub-tile
+template <bool X3>
+__device__ __forceinline__ void park(unsigned char* ring, unsigned ring_w, int u, const Row<X3>& v) {
+    unsigned char* dst = ring + ring_w + (unsigned)((u & 3) * 16 * kRowP<X3>);
+#pragma unroll
+    for (int h = 0; h < (X3 ? 2 : 1); ++h) *reinterpret_cast<u32x4*>(dst + 64 * h) = v.v[h];
 }
 
-template <bool F16>
-__device__ __forceinline__ float widen16(unsigned short u) {
-    if constexpr (F16)
-        return (float)__builtin_bit_cast(_Float16, u);
-    else
-        return __builtin_bit_cast(float, (unsigned)u << 16);
+// A conv block: the 16 pooled outputs of block v (input rows 32v .. 32v+31) from ring rows 32v - 1 .. 32v + 32.
+// Lane (c = r, kq) owns pooled position c of the block: one accumulator set for its even conv position (input rows 2c-1, 2c,
+// 2c+1), one for the odd one (2c, 2c+1, 2c+2), so MaxPool is a max of two registers of the same lane, the four row fragments
+// serve six operands, and every lane ends up with whole channel groups: channels 16j + 4kq .. +3 of its row for every channel
+// tile j, as hi[j] (and lo[j]), handed to sink(hi, lo).  whi(t, j) / wlo(t, j): the A fragments W[n = 16j + r][tap t][8kq .. +7],
+// hi and lo halves (plain: whi are the weights, wlo is not called).  X3 rows hold 32 channel slots per panel but only NT * 16
+// channels are computed: the NTP - NT tiles behind them are handed on as zeros (the next layer multiplies them by zero weights,
+// so they must be finite).  MASKED = false: every output of the block is a valid output of its read.
+template <int NT, bool F16, bool X3, bool MASKED, class WHi, class WLo, class Bias, class Sink>
+__device__ __forceinline__ void conv_block(const unsigned char* ring, int r, int kq, int v, const SubInfo& si, const WHi& whi, const WLo& wlo,
+                                           const Bias& bias, const float unscale, unsigned& sat, Sink&& sink) {
+    constexpr int NH = X3 ? 2 : 1, ROWP = kRowP<X3>;
+    constexpr int NTP = kStoreTiles<NT, X3>;
+    const unsigned ring_r = (unsigned)(2 * r * ROWP + (kq << 4));   // this lane's byte in ring row 2c
+    const int tp0 = si.t0 >> 1, out_len = si.l0 >> 1;
+    u32x2 hi[NTP], lo[NTP];
+#pragma unroll
+    for (int j = 0; j < NTP; ++j) hi[j] = lo[j] = (u32x2){0u, 0u};
+    if (MASKED && tp0 >= out_len) {                             // uniform: every output of the block is zero
+        sink(hi, lo);
+        return;
+    }
+    u32x4 xf[4][NH];                                            // ring rows 32v + 2c + d - 1, d = 0 .. 3
+    // block v = sub-tiles 2v, 2v+1 = ring rows 32 (v & 1) .. +31; row -1 and row 32 wrap inside the 64-row ring
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        // rows 2c + row0 (row0: ring row of lane group c = 0) stay below 64 except for d = 3 of the upper half's last lane group
+        // (row 64 -> 0)
+        unsigned off = (unsigned)((32 * v + d - 1) & (kRing - 1)) * ROWP + ring_r;
+        if (d == 3 || d == 0) off = (unsigned)(((32 * v + 2 * r + d - 1) & (kRing - 1)) * ROWP + (kq << 4));
+#pragma unroll
+        for (int h = 0; h < NH; ++h) xf[d][h] = *reinterpret_cast<const u32x4*>(ring + off + 64 * h);
+    }
+    f32x4 acc[2][NT];                                           // [even / odd conv position][channel tile]
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[e][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#ifndef RS_ABL_NOMFMA
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                acc[e][j] = mfma16<F16>(whi(t, j), xf[t + e][0], acc[e][j]);                 // hi * hi
+                if constexpr (X3) {
+                    acc[e][j] = mfma16<F16>(whi(t, j), xf[t + e][1], acc[e][j]);             // w hi * x lo
+                    acc[e][j] = mfma16<F16>(wlo(t, j), xf[t + e][0], acc[e][j]);             // w lo * x hi  (order of conv_ring_h16)
+                }
+            }
+#else
+    for (int j = 0; j < NT; ++j) acc[0][j] = acc[1][j] = __builtin_bit_cast(f32x4, xf[0][0] ^ xf[1][0] ^ xf[2][0] ^ xf[3][0]);
+#endif
+    const unsigned keep = (!MASKED || tp0 + r < out_len) ? ~0u : 0u;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        // MaxPool, + bias, ReLU: max(e, o) + b == max(e + b, o + b) bit for bit (rounding is monotonic), which is
+        // two v_pk_add_f32 and one v_max3_f32 per channel pair instead of max / add / max per channel
+        const f32x2 b01 = {bias[j][0], bias[j][1]}, b23 = {bias[j][2], bias[j][3]};
+        // x * unscale + b in one rounding (v_pk_fma_f32); unscale = 1 outside half precision: the plain sum, bit for bit
+        const f32x2 us = {unscale, unscale};
+        const f32x2 e01 = __builtin_elementwise_fma((f32x2){acc[0][j][0], acc[0][j][1]}, us, b01),
+                    e23 = __builtin_elementwise_fma((f32x2){acc[0][j][2], acc[0][j][3]}, us, b23);
+        const f32x2 o01 = __builtin_elementwise_fma((f32x2){acc[1][j][0], acc[1][j][1]}, us, b01),
+                    o23 = __builtin_elementwise_fma((f32x2){acc[1][j][2], acc[1][j][3]}, us, b23);
+        const float p0 = fmaxf(fmaxf(e01[0], o01[0]), 0.0f), p1 = fmaxf(fmaxf(e01[1], o01[1]), 0.0f);
+        const float p2 = fmaxf(fmaxf(e23[0], o23[0]), 0.0f), p3 = fmaxf(fmaxf(e23[1], o23[1]), 0.0f);
+        hi[j] = (u32x2){pack2<F16>(p0, p1), pack2<F16>(p2, p3)};
+        if constexpr (F16) sat |= f16_overflow_bits(hi[j][0]) | f16_overflow_bits(hi[j][1]);
+        if constexpr (X3) lo[j] = (u32x2){pack2_lo<F16>(p0, p1, hi[j][0]), pack2_lo<F16>(p2, p3, hi[j][1])};
+        if constexpr (MASKED) {
+            hi[j] &= (u32x2){keep, keep};
+            lo[j] &= (u32x2){keep, keep};
+        }
+    }
+    sink(hi, lo);
 }
-// lo dword of a pair of values whose hi dword (two 16-bit roundings) is `hi`
-template <bool F16>
-__device__ __forceinline__ unsigned pack2_lo(float a, float b, unsigned hi) {
-    return pack2<F16>(a - widen16<F16>((unsigned short)(hi & 0xffffu)), b - widen16<F16>((unsigned short)(hi >> 16)));
+
+// Two channel tiles j, j+1 of a block's hi (h = 1: lo) words, exchanged between the lane rows with v_permlane16_swap_b32 so that
+// every lane ends up with 8 CONSECUTIVE channels - 16j + 16 (kq & 1) + 8 (kq >> 1) .. +7 - of its row
+template <class Words>
+__device__ __forceinline__ u32x4 gather8(const Words& hi, const Words& lo, int j, int h) {
+    const u32x2 wa = h ? lo[j] : hi[j], wb = h ? lo[j + 1] : hi[j + 1];
+    const auto s0 = __builtin_amdgcn_permlane16_swap(wa[0], wb[0], false, false);
+    const auto s1 = __builtin_amdgcn_permlane16_swap(wa[1], wb[1], false, false);
+    return (u32x4){s0[0], s1[0], s0[1], s1[1]};
+}
+
+// The store of a block's 16 output rows: after gather8 the wave writes 64 contiguous bytes per output row and instruction (X3:
+// the hi half-row, then the lo half-row 64 bytes on; the zero tiles of conv_block ride in the pair).
+// st_off: this lane's byte in output row 0 per store, or out of range.  cp_out: row pitch in 16-bit elements (X3: 32-channel
+// panels of [hi x 32 | lo x 32], cp_out / 2 logical channel slots)
+template <int NT, bool X3>
+__device__ __forceinline__ void store_offsets(unsigned (&st_off)[(kStoreTiles<NT, X3> + 1) / 2], int r, int kq, int cp_out) {
+    constexpr int NTP = kStoreTiles<NT, X3>;
+    const int ch_lim = X3 ? cp_out / 2 : cp_out;
+#pragma unroll
+    for (int j = 0; j + 1 < NTP; j += 2) {
+        const int ch = 16 * j + 16 * (kq & 1) + 8 * (kq >> 1);
+        st_off[j / 2] = ch < ch_lim ? (unsigned)(r * cp_out * 2) + (unsigned)phys_col<X3>(ch) * 2u : kOob;
+    }
+    if constexpr (NTP & 1) {
+        const int ch = 16 * (NTP - 1) + 4 * kq;
+        st_off[NTP / 2] = ch < ch_lim ? (unsigned)(r * cp_out * 2) + (unsigned)phys_col<X3>(ch) * 2u : kOob;
+    }
 }
 
 template <bool FUSE0, int NT, bool F16, bool X3>
 __global__ __launch_bounds__(kWaves * 64, X3 ? 2 : NT == 3 ? 3 : RS_STREAM_WGS) void conv_stream_h16_kernel(const StreamArgs a) {
     unsigned sat = 0u;                                          // half precision: a conversion overflowed (raised at the end)
-    constexpr int ROWB = X3 ? 128 : 64;                         // ring row / input row of one panel
     constexpr int NH = X3 ? 2 : 1;                              // 16-byte halves a lane handles per row: hi (and lo)
-    // ring row pitch: 16 bytes more than a row, so that the consumer's ds_read_b128 of every SECOND row (rows 2c + d of
-    // lane group c) and the producer's ds_write_b128 of consecutive rows are both free of bank conflicts without a
-    // swizzle (slot = (5 row + kq) mod 16 resp. (9 row + kq) mod 16 over the 16-lane groups of ds_read_b128)
-    constexpr int ROWP = ROWB + 16;
+    constexpr int ROWP = kRowP<X3>;
     __shared__ __attribute__((aligned(16))) unsigned char ring_all[kWaves * kRing * ROWP];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -161,9 +300,7 @@ __global__ __launch_bounds__(kWaves * 64, X3 ? 2 : NT == 3 ? 3 : RS_STREAM_WGS) 
     f32x4 bias[NT];                                             // channels 16j + 4kq + q of this lane's accumulators
 #pragma unroll
     for (int j = 0; j < NT; ++j) bias[j] = *reinterpret_cast<const f32x4*>(a.bias + 16 * j + 4 * kq);
-    // layer 0 on the f32-input MFMA (v_mfma_f32_16x16x4_f32, K = 3 taps + one zero column; bit-exact fmaf chains from
-    // the accumulator input, which carries the bias: the same chain as conv0_kernel): A = W0[channel 16m + r][tap kq],
-    // C = bias of channels 16m + 4kq + i
+    // layer 0 (conv0_subtile): A = W0[channel 16m + r][tap kq], C = bias of channels 16m + 4kq + i
     float w0t[2] = {0.f, 0.f};
     f32x4 cb[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     if constexpr (FUSE0) {
@@ -178,7 +315,7 @@ __global__ __launch_bounds__(kWaves * 64, X3 ? 2 : NT == 3 ? 3 : RS_STREAM_WGS) 
         }
     }
     // ring slot (16 bytes = 8 channels) this lane writes: a loaded row arrives as channels 8kq .., a computed layer-0
-    // row as channels 16 (kq & 1) + 8 (kq >> 1) .. (see conv0)
+    // row as channels 16 (kq & 1) + 8 (kq >> 1) .. (conv0_subtile)
     const int wslot = FUSE0 ? 2 * (kq & 1) + (kq >> 1) : kq;
 
     // ---- row bookkeeping ------------------------------------------------------------------------------
@@ -186,9 +323,6 @@ __global__ __launch_bounds__(kWaves * 64, X3 ? 2 : NT == 3 ? 3 : RS_STREAM_WGS) 
     // (read, first position, valid rows) of the block it consumes next in scalar registers and advances them by 32
     // rows per block; a sub-tile is described by the position of its first row in its read and the read's valid rows.
     const const_len_ptr clen = as_const_len(a.len);
-    struct SubInfo {
-        int t0, l0;                                             // first row's position in its read; valid rows of the read
-    };
     auto len_of = [&](int b) { return (b >= 0 && b < a.n_reads) ? clen[b] >> a.shift_in : 0; };
 
     // ---- producer: one 16-row sub-tile of input rows into the ring -----------------------------------
@@ -219,112 +353,37 @@ __global__ __launch_bounds__(kWaves * 64, X3 ? 2 : NT == 3 ? 3 : RS_STREAM_WGS) 
             if constexpr (NL == 2) dst.v[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, off + 64u, 0, 0);
         }
     };
-    struct Row {
-        u32x4 v[NH];                                            // this lane's 8 channels of its row: hi (and lo)
-    };
-    // Layer 0 of 16 pooled rows on the matrix pipe: columns = pooled rows, one MFMA for their even conv positions and
-    // one for the odd ones per 16-channel tile, so MaxPool + ReLU is one v_max3_f32 per value, in-lane.  The lane
-    // then holds channels 4kq .. +3 and 16 + 4kq .. +3 of its row; v_permlane16_swap_b32 turns that into 8
-    // consecutive channels (16 (kq & 1) + 8 (kq >> 1) ..), which is a 16-byte slot of the ring row in natural order.
-    auto conv0 = [&](const u32x4& raw) {
-        const unsigned ue = raw[0], uo = raw[1];               // (bit_cast of a vector ELEMENT lvalue reads element 0)
-        const float xe = __builtin_bit_cast(float, ue), xo = __builtin_bit_cast(float, uo);
-        float o[2][4];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-#ifdef RS_ABL_NOCONV0
-            const f32x4 e = cb[m] * xe, f = cb[m] * xo;
-#else
-            const f32x4 e = __builtin_amdgcn_mfma_f32_16x16x4f32(w0t[m], xe, cb[m], 0, 0, 0);
-            const f32x4 f = __builtin_amdgcn_mfma_f32_16x16x4f32(w0t[m], xo, cb[m], 0, 0, 0);
-#endif
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[m][i] = fmaxf(fmaxf(e[i], f[i]), 0.0f);
-        }
-        unsigned w[NH][2][2];                                   // [hi / lo][tile][dword]
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            w[0][m][0] = pack2<F16>(o[m][0], o[m][1]);
-            w[0][m][1] = pack2<F16>(o[m][2], o[m][3]);
-            if constexpr (F16) sat |= f16_overflow_bits(w[0][m][0]) | f16_overflow_bits(w[0][m][1]);
-            if constexpr (X3) {
-                w[1][m][0] = pack2_lo<F16>(o[m][0], o[m][1], w[0][m][0]);
-                w[1][m][1] = pack2_lo<F16>(o[m][2], o[m][3], w[0][m][1]);
-            }
-        }
-        Row out;
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            const auto s0 = __builtin_amdgcn_permlane16_swap(w[h][0][0], w[h][1][0], false, false);
-            const auto s1 = __builtin_amdgcn_permlane16_swap(w[h][0][1], w[h][1][1], false, false);
-            out.v[h] = (u32x4){s0[0], s1[0], s0[1], s1[1]};
-        }
-        return out;
-    };
     const unsigned ring_w = (unsigned)(r * ROWP + (wslot << 4));   // this lane's byte in ring row 0 of a sub-tile
-    auto park = [&](int u, const Row& v) {                     // sub-tile u occupies ring rows 16 (u & 3) ..
-        unsigned char* dst = ring + ring_w + (unsigned)((u & 3) * 16 * ROWP);
-#pragma unroll
-        for (int h = 0; h < NH; ++h) *reinterpret_cast<u32x4*>(dst + 64 * h) = v.v[h];
-    };
     // INTERIOR: every row of the sub-tile is a valid row of its read
     auto produce_fast = [&](int u, const Raw& raw) {
-        Row v;
+        Row<X3> v;
         if constexpr (FUSE0) {
-            v = conv0(raw.v[0]);
+            v = conv0_subtile<F16, X3>(raw.v[0][0], raw.v[0][1], w0t, cb, sat);
         } else {
 #pragma unroll
             for (int h = 0; h < NH; ++h) v.v[h] = raw.v[h];
         }
-        park(u, v);
+        park<X3>(ring, ring_w, u, v);
     };
-    // GENERAL: rows beyond the read's length are zero rows (loaded rows already are; computed ones are masked); a
-    // sub-tile wholly beyond it costs no arithmetic
+    // GENERAL: rows beyond the read's length are zero rows (loaded rows already are; computed ones are masked)
     auto produce = [&](int u, const Raw& raw, const SubInfo& si) {
-        Row v;
+        Row<X3> v;
         if constexpr (FUSE0) {
-            if (si.t0 >= si.l0) {
-#pragma unroll
-                for (int h = 0; h < NH; ++h) v.v[h] = (u32x4){0u, 0u, 0u, 0u};
-            } else {
-                v = conv0(raw.v[0]);
-                const unsigned keep = si.t0 + r < si.l0 ? ~0u : 0u;
-#pragma unroll
-                for (int h = 0; h < NH; ++h) v.v[h] &= (u32x4){keep, keep, keep, keep};
-            }
+            v = conv0_subtile_masked<F16, X3>(raw.v[0][0], raw.v[0][1], w0t, cb, sat, r, si);
         } else {
 #pragma unroll
             for (int h = 0; h < NH; ++h) v.v[h] = raw.v[h];
         }
-        park(u, v);
+        park<X3>(ring, ring_w, u, v);
     };
 
-    // ---- consumer: the 16 pooled outputs of block v (input rows 32v .. 32v+31) from ring rows 32v - 1 .. 32v + 32.
-    // Lane (c = lane & 15, kq) owns pooled position c of the block: one accumulator set for its even conv position
-    // (input rows 2c-1, 2c, 2c+1), one for the odd one (2c, 2c+1, 2c+2), so MaxPool is a max of two registers of the
-    // same lane, the four row fragments serve six operands, and every lane stores whole channel groups.
-    // byte offset of logical channel ch inside an output row (X3: 32-channel panels of [hi x 32 | lo x 32]) and the
-    // number of logical channel slots of a row
-    auto ch_off = [&](int ch) { return (unsigned)(X3 ? ((ch >> 5) << 6) + (ch & 31) : ch) * 2u; };
-    const int ch_lim = X3 ? a.cp_out / 2 : a.cp_out;
-    // Stores.  A lane holds channels 16j + 4kq .. +3 of its row for every channel tile j (8 bytes of 16-bit values).
-    // Two tiles j, j+1 are exchanged between the lane rows with v_permlane16_swap_b32 so that every lane ends up with
-    // 8 CONSECUTIVE channels - 16j + 16 (kq & 1) + 8 (kq >> 1) .. +7 - and the wave writes 64 contiguous bytes per
-    // output row and instruction (X3: the hi half-row, then the lo half-row 64 bytes on).  X3 rows hold 32 channel
-    // slots per panel but only NT * 16 channels are computed: the slots behind them are written as zeros (the next
-    // layer multiplies them by zero weights, so they must be finite) - they ride in the pair.
-    constexpr int NTP = X3 ? 2 * ((NT + 1) / 2) : NT;           // channel tiles written per row
-    unsigned st_off[(NTP + 1) / 2];                             // this lane's byte in output row 0 per store, or out of range
-#pragma unroll
-    for (int j = 0; j + 1 < NTP; j += 2) {
-        const int ch = 16 * j + 16 * (kq & 1) + 8 * (kq >> 1);
-        st_off[j / 2] = ch < ch_lim ? (unsigned)(r * a.cp_out * 2) + ch_off(ch) : kOob;
-    }
-    if constexpr (NTP & 1) {
-        const int ch = 16 * (NTP - 1) + 4 * kq;
-        st_off[NTP / 2] = ch < ch_lim ? (unsigned)(r * a.cp_out * 2) + ch_off(ch) : kOob;
-    }
+    // ---- consumer: block v from the ring (conv_block), stored
+    constexpr int NTP = kStoreTiles<NT, X3>;
+    unsigned st_off[(NTP + 1) / 2];
+    store_offsets<NT, X3>(st_off, r, kq, a.cp_out);
     const unsigned blk_bytes = 32u * (unsigned)a.cp_out;        // 16 output rows
+    // (the store loop is written out here and in conv_stream012_h16_kernel: as one shared function it compiles, in the FUSE0
+    // variants, to ONE store sequence for the three paths of a block instead of one per path - DESIGN.md 13)
     auto store_rows = [&](int v, const u32x2 (&hi)[NTP], const u32x2 (&lo)[NTP]) {
 #ifdef RS_ABL_NOSTORE
         const unsigned base = kOob;
@@ -335,10 +394,7 @@ __global__ __launch_bounds__(kWaves * 64, X3 ? 2 : NT == 3 ? 3 : RS_STREAM_WGS) 
         for (int j = 0; j + 1 < NTP; j += 2) {
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
-                const u32x2 wa = h ? lo[j] : hi[j], wb = h ? lo[j + 1] : hi[j + 1];
-                const auto s0 = __builtin_amdgcn_permlane16_swap(wa[0], wb[0], false, false);
-                const auto s1 = __builtin_amdgcn_permlane16_swap(wa[1], wb[1], false, false);
-                __builtin_amdgcn_raw_buffer_store_b128((u32x4){s0[0], s1[0], s0[1], s1[1]}, rs_y,
+                __builtin_amdgcn_raw_buffer_store_b128(gather8(hi, lo, j, h), rs_y,
                                                        ((base | st_off[j / 2]) & kOob) ? kOob : base + st_off[j / 2] + 64u * h, 0, 0);
             }
         }
@@ -346,73 +402,11 @@ __global__ __launch_bounds__(kWaves * 64, X3 ? 2 : NT == 3 ? 3 : RS_STREAM_WGS) 
             __builtin_amdgcn_raw_buffer_store_b64(hi[NTP - 1], rs_y,
                                                   ((base | st_off[NTP / 2]) & kOob) ? kOob : base + st_off[NTP / 2], 0, 0);
     };
-    const unsigned ring_r = (unsigned)(2 * r * ROWP + (kq << 4));   // this lane's byte in ring row 2c
-    // MASKED = false: every output of the block is a valid output of its read
+    auto whi = [&](int t, int j) -> const u32x4& { return wf[0][t][j]; };
+    auto wlo = [&](int t, int j) -> const u32x4& { return wf[NH - 1][t][j]; };
     auto consume = [&](int v, const SubInfo& si, auto MASKED) {
-        constexpr bool masked = decltype(MASKED)::value;
-        const int tp0 = si.t0 >> 1, out_len = si.l0 >> 1;
-        u32x2 hi[NTP], lo[NTP];
-#pragma unroll
-        for (int j = 0; j < NTP; ++j) hi[j] = lo[j] = (u32x2){0u, 0u};
-        if (masked && tp0 >= out_len) {                         // uniform: every output of the block is zero
-            store_rows(v, hi, lo);
-            return;
-        }
-        u32x4 xf[4][NH];                                        // ring rows 32v + 2c + d - 1, d = 0 .. 3
-        // block v = sub-tiles 2v, 2v+1 = ring rows 32 (v & 1) .. +31; row -1 and row 32 wrap inside the 64-row ring
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const unsigned row0 = (unsigned)((32 * v + d - 1) & (kRing - 1));       // ring row of lane group c = 0
-            // rows 2c + row0 stay below 64 except for d = 3 of the upper half's last lane group (row 64 -> 0)
-            unsigned off = row0 * ROWP + ring_r;
-            if (d == 3 || d == 0) off = (unsigned)(((32 * v + 2 * r + d - 1) & (kRing - 1)) * ROWP + (kq << 4));
-#pragma unroll
-            for (int h = 0; h < NH; ++h) xf[d][h] = *reinterpret_cast<const u32x4*>(ring + off + 64 * h);
-        }
-        f32x4 acc[2][NT];                                       // [even / odd conv position][channel tile]
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[e][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#ifndef RS_ABL_NOMFMA
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    acc[e][j] = mfma16<F16>(wf[0][t][j], xf[t + e][0], acc[e][j]);               // hi * hi
-                    if constexpr (X3) {
-                        acc[e][j] = mfma16<F16>(wf[0][t][j], xf[t + e][1], acc[e][j]);           // w hi * x lo
-                        acc[e][j] = mfma16<F16>(wf[1][t][j], xf[t + e][0], acc[e][j]);           // w lo * x hi  (order of conv_ring_h16)
-                    }
-                }
-#else
-        for (int j = 0; j < NT; ++j) acc[0][j] = acc[1][j] = __builtin_bit_cast(f32x4, xf[0][0] ^ xf[1][0] ^ xf[2][0] ^ xf[3][0]);
-#endif
-        const unsigned keep = (!masked || tp0 + r < out_len) ? ~0u : 0u;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            // MaxPool, + bias, ReLU: max(e, o) + b == max(e + b, o + b) bit for bit (rounding is monotonic), which is
-            // two v_pk_add_f32 and one v_max3_f32 per channel pair instead of max / add / max per channel
-            const f32x2 b01 = {bias[j][0], bias[j][1]}, b23 = {bias[j][2], bias[j][3]};
-            // x * unscale + b in one rounding (v_pk_fma_f32); unscale = 1 outside half precision: the plain sum, bit for bit
-            const f32x2 us = {a.unscale, a.unscale};
-            const f32x2 e01 = __builtin_elementwise_fma((f32x2){acc[0][j][0], acc[0][j][1]}, us, b01),
-                        e23 = __builtin_elementwise_fma((f32x2){acc[0][j][2], acc[0][j][3]}, us, b23);
-            const f32x2 o01 = __builtin_elementwise_fma((f32x2){acc[1][j][0], acc[1][j][1]}, us, b01),
-                        o23 = __builtin_elementwise_fma((f32x2){acc[1][j][2], acc[1][j][3]}, us, b23);
-            const float p0 = fmaxf(fmaxf(e01[0], o01[0]), 0.0f), p1 = fmaxf(fmaxf(e01[1], o01[1]), 0.0f);
-            const float p2 = fmaxf(fmaxf(e23[0], o23[0]), 0.0f), p3 = fmaxf(fmaxf(e23[1], o23[1]), 0.0f);
-            hi[j] = (u32x2){pack2<F16>(p0, p1), pack2<F16>(p2, p3)};
-            if constexpr (F16) sat |= f16_overflow_bits(hi[j][0]) | f16_overflow_bits(hi[j][1]);
-            if constexpr (X3) lo[j] = (u32x2){pack2_lo<F16>(p0, p1, hi[j][0]), pack2_lo<F16>(p2, p3, hi[j][1])};
-            if constexpr (masked) {
-                hi[j] &= (u32x2){keep, keep};
-                lo[j] &= (u32x2){keep, keep};
-            }
-        }
-        store_rows(v, hi, lo);
+        conv_block<NT, F16, X3, decltype(MASKED)::value>(ring, r, kq, v, si, whi, wlo, bias, a.unscale, sat,
+                                                         [&](const auto& hi, const auto& lo) { store_rows(v, hi, lo); });
     };
 
     // ---- run: the wave owns blocks u0 .. u1-1, i.e. 16-row sub-tiles 2 u0 .. 2 u1 - 1, and also produces the sub-tile
@@ -508,9 +502,8 @@ __global__ __launch_bounds__((X3 ? 8 : 4) * 64, X3 ? 1 : 3) void conv_stream012_
     unsigned sat = 0u;
     constexpr int NW = X3 ? 8 : 4;                              // waves per workgroup
     constexpr int NT1 = 2;
-    constexpr int ROWB = X3 ? 128 : 64;
     constexpr int NH = X3 ? 2 : 1;
-    constexpr int ROWP = ROWB + 16;
+    constexpr int ROWP = kRowP<X3>;
     constexpr int W2ROWS = 3 * 16 * NT2;
     __shared__ __attribute__((aligned(16))) unsigned char ring_all[NW * 2 * kRing * ROWP];
     __shared__ __attribute__((aligned(16))) unsigned char w2lo[X3 ? W2ROWS * 64 : 16];
@@ -572,9 +565,6 @@ __global__ __launch_bounds__((X3 ? 8 : 4) * 64, X3 ? 1 : 3) void conv_stream012_
     const int wslot = 2 * (kq & 1) + (kq >> 1);                 // ring slot of the 8 consecutive channels a lane gathers
 
     const const_len_ptr clen = as_const_len(a.len);
-    struct SubInfo {
-        int t0, l0;                                             // first input row's position in its read; valid input rows
-    };
     auto len_of = [&](int b) { return (b >= 0 && b < a.n_reads) ? clen[b] : 0; };   // raw samples
 
     // ---- layer 0: sub-tiles of 16 layer-1 input rows into ring 1 ---------------------------------------
@@ -582,152 +572,27 @@ __global__ __launch_bounds__((X3 ? 8 : 4) * 64, X3 ? 1 : 3) void conv_stream012_
     u32x2 pre[D];
     const unsigned lane_off = (unsigned)(2 * r - 1 + kq + 4) * 4u;
     auto issue_load = [&](int u, u32x2& dst) { dst = __builtin_amdgcn_raw_buffer_load_b64(rs_x, lane_off + (unsigned)u * 128u, 0, 0); };
-    struct Row {
-        u32x4 v[NH];
-    };
-    auto conv0 = [&](const u32x2& raw) {
-        const unsigned ue = raw[0], uo = raw[1];
-        const float xe = __builtin_bit_cast(float, ue), xo = __builtin_bit_cast(float, uo);
-        float o[2][4];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const f32x4 e = __builtin_amdgcn_mfma_f32_16x16x4f32(w0t[m], xe, cb[m], 0, 0, 0);
-            const f32x4 f = __builtin_amdgcn_mfma_f32_16x16x4f32(w0t[m], xo, cb[m], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[m][i] = fmaxf(fmaxf(e[i], f[i]), 0.0f);
-        }
-        unsigned w[NH][2][2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            w[0][m][0] = pack2<F16>(o[m][0], o[m][1]);
-            w[0][m][1] = pack2<F16>(o[m][2], o[m][3]);
-            if constexpr (F16) sat |= f16_overflow_bits(w[0][m][0]) | f16_overflow_bits(w[0][m][1]);
-            if constexpr (X3) {
-                w[1][m][0] = pack2_lo<F16>(o[m][0], o[m][1], w[0][m][0]);
-                w[1][m][1] = pack2_lo<F16>(o[m][2], o[m][3], w[0][m][1]);
-            }
-        }
-        Row out;
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            const auto s0 = __builtin_amdgcn_permlane16_swap(w[h][0][0], w[h][1][0], false, false);
-            const auto s1 = __builtin_amdgcn_permlane16_swap(w[h][0][1], w[h][1][1], false, false);
-            out.v[h] = (u32x4){s0[0], s1[0], s0[1], s1[1]};
-        }
-        return out;
-    };
     const unsigned ring_w = (unsigned)(r * ROWP + (wslot << 4));
-    auto park = [&](unsigned char* ring, int u, const Row& v) {   // sub-tile u occupies ring rows 16 (u & 3) ..
-        unsigned char* dst = ring + ring_w + (unsigned)((u & 3) * 16 * ROWP);
-#pragma unroll
-        for (int h = 0; h < NH; ++h) *reinterpret_cast<u32x4*>(dst + 64 * h) = v.v[h];
-    };
-    auto produce_fast = [&](int u, const u32x2& raw) { park(ring1, u, conv0(raw)); };
+    auto produce_fast = [&](int u, const u32x2& raw) { park<X3>(ring1, ring_w, u, conv0_subtile<F16, X3>(raw[0], raw[1], w0t, cb, sat)); };
     auto produce = [&](int u, const u32x2& raw, const SubInfo& si) {
-        Row v;
-        if (si.t0 >= si.l0) {
-#pragma unroll
-            for (int h = 0; h < NH; ++h) v.v[h] = (u32x4){0u, 0u, 0u, 0u};
-        } else {
-            v = conv0(raw);
-            const unsigned keep = si.t0 + r < si.l0 ? ~0u : 0u;
-#pragma unroll
-            for (int h = 0; h < NH; ++h) v.v[h] &= (u32x4){keep, keep, keep, keep};
-        }
-        park(ring1, u, v);
+        park<X3>(ring1, ring_w, u, conv0_subtile_masked<F16, X3>(raw[0], raw[1], w0t, cb, sat, r, si));
     };
 
-    // ---- a conv block: 16 pooled outputs of block v from the 34 ring rows 32v - 1 .. 32v + 32 ------------
-    const unsigned ring_r = (unsigned)(2 * r * ROWP + (kq << 4));
-    auto block = [&](const unsigned char* ring, int v, const SubInfo& si, auto MASKED, auto NTc, const auto& whi, const auto& wlo,
-                     const auto& bias, const float unscale, auto&& sink) {
-        constexpr bool masked = decltype(MASKED)::value;
-        constexpr int NT = decltype(NTc)::value;
-        constexpr int NTP = X3 ? 2 * ((NT + 1) / 2) : NT;
-        const int tp0 = si.t0 >> 1, out_len = si.l0 >> 1;
-        u32x2 hi[NTP], lo[NTP];
-#pragma unroll
-        for (int j = 0; j < NTP; ++j) hi[j] = lo[j] = (u32x2){0u, 0u};
-        if (masked && tp0 >= out_len) {
-            sink(hi, lo);
-            return;
-        }
-        u32x4 xf[4][NH];
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            unsigned off = (unsigned)((32 * v + d - 1) & (kRing - 1)) * ROWP + ring_r;
-            if (d == 3 || d == 0) off = (unsigned)(((32 * v + 2 * r + d - 1) & (kRing - 1)) * ROWP + (kq << 4));
-#pragma unroll
-            for (int h = 0; h < NH; ++h) xf[d][h] = *reinterpret_cast<const u32x4*>(ring + off + 64 * h);
-        }
-        f32x4 acc[2][NT];
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[e][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    acc[e][j] = mfma16<F16>(whi(t, j), xf[t + e][0], acc[e][j]);                 // hi * hi
-                    if constexpr (X3) {
-                        acc[e][j] = mfma16<F16>(whi(t, j), xf[t + e][1], acc[e][j]);             // w hi * x lo
-                        acc[e][j] = mfma16<F16>(wlo(t, j), xf[t + e][0], acc[e][j]);             // w lo * x hi  (order of conv_ring_h16)
-                    }
-                }
-        const unsigned keep = (!masked || tp0 + r < out_len) ? ~0u : 0u;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const f32x2 b01 = {bias[j][0], bias[j][1]}, b23 = {bias[j][2], bias[j][3]};
-            const f32x2 us = {unscale, unscale};
-            const f32x2 e01 = __builtin_elementwise_fma((f32x2){acc[0][j][0], acc[0][j][1]}, us, b01),
-                        e23 = __builtin_elementwise_fma((f32x2){acc[0][j][2], acc[0][j][3]}, us, b23);
-            const f32x2 o01 = __builtin_elementwise_fma((f32x2){acc[1][j][0], acc[1][j][1]}, us, b01),
-                        o23 = __builtin_elementwise_fma((f32x2){acc[1][j][2], acc[1][j][3]}, us, b23);
-            const float p0 = fmaxf(fmaxf(e01[0], o01[0]), 0.0f), p1 = fmaxf(fmaxf(e01[1], o01[1]), 0.0f);
-            const float p2 = fmaxf(fmaxf(e23[0], o23[0]), 0.0f), p3 = fmaxf(fmaxf(e23[1], o23[1]), 0.0f);
-            hi[j] = (u32x2){pack2<F16>(p0, p1), pack2<F16>(p2, p3)};
-            if constexpr (F16) sat |= f16_overflow_bits(hi[j][0]) | f16_overflow_bits(hi[j][1]);
-            if constexpr (X3) lo[j] = (u32x2){pack2_lo<F16>(p0, p1, hi[j][0]), pack2_lo<F16>(p2, p3, hi[j][1])};
-            if constexpr (masked) {
-                hi[j] &= (u32x2){keep, keep};
-                lo[j] &= (u32x2){keep, keep};
-            }
-        }
-        sink(hi, lo);
-    };
-    // layer 1: weights in registers, the block becomes sub-tile v of ring 2 (8 consecutive channels per lane)
+    // ---- layer 1: weights in registers, the block becomes sub-tile v of ring 2 (8 consecutive channels per lane)
     auto w1hi = [&](int t, int j) -> const u32x4& { return wf1[0][t][j]; };
     auto w1lo = [&](int t, int j) -> const u32x4& { return wf1[NH - 1][t][j]; };
     auto block1 = [&](int v, const SubInfo& si, auto MASKED) {
-        block(ring1, v, si, MASKED, std::integral_constant<int, NT1>{}, w1hi, w1lo, bias1, a.unscale1, [&](const auto& hi, const auto& lo) {
-            Row row;
+        conv_block<NT1, F16, X3, decltype(MASKED)::value>(ring1, r, kq, v, si, w1hi, w1lo, bias1, a.unscale1, sat, [&](const auto& hi, const auto& lo) {
+            Row<X3> row;
 #pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                const u32x2 wa = h ? lo[0] : hi[0], wb = h ? lo[1] : hi[1];
-                const auto s0 = __builtin_amdgcn_permlane16_swap(wa[0], wb[0], false, false);
-                const auto s1 = __builtin_amdgcn_permlane16_swap(wa[1], wb[1], false, false);
-                row.v[h] = (u32x4){s0[0], s1[0], s0[1], s1[1]};
-            }
-            park(ring2, v, row);
+            for (int h = 0; h < NH; ++h) row.v[h] = gather8(hi, lo, 0, h);
+            park<X3>(ring2, ring_w, v, row);
         });
     };
-    // layer 2: hi weights in registers, lo weights from LDS; the block is stored
-    const int ch_lim = X3 ? a.cp_out / 2 : a.cp_out;
-    auto ch_off = [&](int ch) { return (unsigned)(X3 ? ((ch >> 5) << 6) + (ch & 31) : ch) * 2u; };
-    constexpr int NTP2 = X3 ? 2 * ((NT2 + 1) / 2) : NT2;
+    // ---- layer 2: hi weights in registers, lo weights from LDS; the block is stored
+    constexpr int NTP2 = kStoreTiles<NT2, X3>;
     unsigned st_off[(NTP2 + 1) / 2];
-#pragma unroll
-    for (int j = 0; j + 1 < NTP2; j += 2) {
-        const int ch = 16 * j + 16 * (kq & 1) + 8 * (kq >> 1);
-        st_off[j / 2] = ch < ch_lim ? (unsigned)(r * a.cp_out * 2) + ch_off(ch) : kOob;
-    }
-    if constexpr (NTP2 & 1) {
-        const int ch = 16 * (NTP2 - 1) + 4 * kq;
-        st_off[NTP2 / 2] = ch < ch_lim ? (unsigned)(r * a.cp_out * 2) + ch_off(ch) : kOob;
-    }
+    store_offsets<NT2, X3>(st_off, r, kq, a.cp_out);
     const unsigned blk_bytes = 32u * (unsigned)a.cp_out;
     auto w2hi = [&](int t, int j) -> const u32x4& { return wf2[t][j]; };
     auto block2 = [&](int v, const SubInfo& si, auto MASKED) {
@@ -742,16 +607,18 @@ __global__ __launch_bounds__((X3 ? 8 : 4) * 64, X3 ? 1 : 3) void conv_stream012_
                 }
         }
         auto w2l = [&](int t, int j) -> const u32x4& { return wl[t][j]; };
-        block(ring2, v, si, MASKED, std::integral_constant<int, NT2>{}, w2hi, w2l, bias2, a.unscale2, [&](const auto& hi, const auto& lo) {
+        conv_block<NT2, F16, X3, decltype(MASKED)::value>(ring2, r, kq, v, si, w2hi, w2l, bias2, a.unscale2, sat,
+                                                          [&](const auto& hi, const auto& lo) {
+#ifdef RS_ABL_NOSTORE
+            const unsigned base = kOob;
+#else
             const unsigned base = v < a.n_sub ? (unsigned)v * blk_bytes : kOob;
+#endif
 #pragma unroll
             for (int j = 0; j + 1 < NTP2; j += 2) {
 #pragma unroll
                 for (int h = 0; h < NH; ++h) {
-                    const u32x2 wa = h ? lo[j] : hi[j], wb = h ? lo[j + 1] : hi[j + 1];
-                    const auto s0 = __builtin_amdgcn_permlane16_swap(wa[0], wb[0], false, false);
-                    const auto s1 = __builtin_amdgcn_permlane16_swap(wa[1], wb[1], false, false);
-                    __builtin_amdgcn_raw_buffer_store_b128((u32x4){s0[0], s1[0], s0[1], s1[1]}, rs_y,
+                    __builtin_amdgcn_raw_buffer_store_b128(gather8(hi, lo, j, h), rs_y,
                                                            ((base | st_off[j / 2]) & kOob) ? kOob : base + st_off[j / 2] + 64u * h, 0, 0);
                 }
             }

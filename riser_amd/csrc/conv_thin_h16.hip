@@ -18,20 +18,13 @@
 // One workgroup per tile, no tile walk (a thin launch is tens to hundreds of tiles).  The launch planner (convnet_forward.hpp: select_kernel) takes this
 // kernel where its estimate beats the ring's.
 #include "common.hpp"
+#include "conv_h16_device.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace rs {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kThreads = 512;
 constexpr int kBM = 64, kBN = 32;
@@ -42,7 +35,6 @@ constexpr int kPieces = kXPieces + kWPieces;    // 21 per panel
 constexpr int kPerWave = (kPieces + 7) / 8;     // 3 per wave (the last slots re-issue the last piece)
 constexpr int kStage = (kXRows + 3 * kBN) * 128;
 constexpr int kStages = 3;
-constexpr unsigned kOob = 0x80000000u;
 
 struct ThinArgs {
     const unsigned short* x;     // [rows_in][cpx_in]  panels [hi x 32 | lo x 32]
@@ -59,38 +51,6 @@ struct ThinArgs {
     int n_ntiles;
     int tail;                    // the last panel is the merged tail: its three taps are one K step (conv_ring_h16.hip: TAIL)
 };
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <bool F16>
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    if constexpr (F16)
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-    else
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-template <bool F16>
-__device__ __forceinline__ float widen16(unsigned short u) {
-    if constexpr (F16)
-        return (float)__builtin_bit_cast(_Float16, u);
-    else
-        return __builtin_bit_cast(float, (unsigned)u << 16);
-}
-__device__ __forceinline__ float swap_pair(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-}
-// one LDS-DMA piece: lane l's 16 bytes at rsrc + voff land at LDS byte lds_addr + 16 l (zeros if voff is out of range)
-__device__ __forceinline__ void dma_piece(unsigned voff, const __amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr) {
-    const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :: "v"(voff), "s"(m0v), "s"(rsrc) : "memory");
-}
 
 template <bool F16>
 __global__ __launch_bounds__(kThreads) void conv_thin_h16_kernel(const ThinArgs a) {
@@ -195,10 +155,10 @@ __global__ __launch_bounds__(kThreads) void conv_thin_h16_kernel(const ThinArgs 
 
     // ---- epilogue (conv_ring_h16.hip's, MT = NT = 1): bias + ReLU + MaxPool in registers, a wave-private image of 8 pooled
     // rows x 16 channels x (hi, lo) in LDS, out in 16-byte pieces
-    constexpr int PW = 4, PITCH = PW * 16 + 16, NPIECE = 8 * PW;
+    using Epi = EpiImage<1, true>;
+    constexpr int PW = Epi::PW, PITCH = Epi::PITCH, NPIECE = Epi::NPIECE;
     unsigned char* scr = lds + wave * (8 * PITCH);
     const float bias = a.bias[n0 + wn * 16 + r];
-    const float us = a.unscale;
     const bool odd = r & 1;
     const int orow0 = (m0 + wm * 16) >> 1;                           // first of the wave's 8 pooled rows
     unsigned keep;
@@ -207,22 +167,18 @@ __global__ __launch_bounds__(kThreads) void conv_thin_h16_kernel(const ThinArgs 
         const int b = orow / a.P_out, t = orow - b * a.P_out;
         keep = (b < a.n_blocks && t < (as_const_len(a.len)[min(b, a.n_blocks - 1)] >> a.shift_out)) ? ~0u : 0u;
     }
-    const float v0 = fmaxf(fmaxf(fmaf(acc[0], us, bias), fmaf(acc[1], us, bias)), 0.0f);
-    const float v1 = fmaxf(fmaxf(fmaf(acc[2], us, bias), fmaf(acc[3], us, bias)), 0.0f);
-    const float got = swap_pair(odd ? v0 : v1);
-    const float ca = odd ? got : v0, cb_ = odd ? v1 : got;          // channels (r & ~1, r | 1) of row 2 g + odd
-    const unsigned hi = pack2<F16>(ca, cb_);
-    if constexpr (F16) raise_saturated(a.sat, f16_overflow_bits(hi));
+    unsigned sat = 0u;
+    const u32x2 hl = pool_pack_pair<F16, true>(acc, a.unscale, bias, odd, keep, sat);
+    if constexpr (F16) raise_saturated(a.sat, sat);
     unsigned char* dst = scr + (2 * g + (odd ? 1 : 0)) * PITCH + (r & ~1) * 2;
-    *reinterpret_cast<unsigned*>(dst) = hi & keep;
-    *reinterpret_cast<unsigned*>(dst + 32) = keep &
-        pack2<F16>(ca - widen16<F16>((unsigned short)(hi & 0xffffu)), cb_ - widen16<F16>((unsigned short)(hi >> 16)));
+    *reinterpret_cast<unsigned*>(dst) = hl[0];
+    *reinterpret_cast<unsigned*>(dst + 32) = hl[1];
     // (LDS operations of one wave execute in order: the image needs no wait between its writes and its reads)
     if (lane < NPIECE) {
         const int row8 = lane / PW, part = lane - row8 * PW;
         const int orow = orow0 + row8;
         const int col = n0 + wn * 16 + 8 * (part & 1);
-        const int elem = ((col >> 5) << 6) + (col & 31) + 32 * (part >> 1);
+        const int elem = phys_col<true>(col) + 32 * (part >> 1);
         const bool ok = 2 * orow < a.rows_in;
         const u32x4 v = *reinterpret_cast<const u32x4*>(scr + row8 * PITCH + part * 16);
         __builtin_amdgcn_raw_buffer_store_b128(v, rs_y, ok ? (unsigned)(orow * a.cpx_out + elem) * 2u : kOob, 0, 0);

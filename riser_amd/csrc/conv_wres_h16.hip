@@ -17,6 +17,7 @@
 // Same MFMA sequence per accumulator as conv_ring_h16.hip (panel -> tap -> hi*hi, lo*hi, hi*lo resp. h0*h0, h1*h1), same
 // epilogue arithmetic: results are bit-identical to the ring kernel (RS_H16_WRES=0 selects it; tests compare the two).
 #include "common.hpp"
+#include "conv_h16_device.hpp"
 #include "tile_walk.hpp"
 
 #include <algorithm>
@@ -25,18 +26,9 @@
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kThreads = 512;
 constexpr int kRowB = 128;                      // bytes of an LDS row (one panel of one position / output channel)
 constexpr int kPieceRows = 1024 / kRowB;        // rows per DMA piece (one wave instruction)
-constexpr unsigned kOob = 0x80000000u;
 
 struct WresArgs {
     const unsigned short* x;     // [rows_in][cpx_in]
@@ -55,41 +47,6 @@ struct WresArgs {
     int n_panels, n_alloc, n_reads, shift_out;
     WalkArgs walk;               // n_ntiles == 1
 };
-
-template <bool F16>
-__device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    if constexpr (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <bool F16>
-__device__ __forceinline__ float widen16(unsigned short u) {
-    if constexpr (F16)
-        return (float)__builtin_bit_cast(_Float16, u);
-    else
-        return __builtin_bit_cast(float, (unsigned)u << 16);
-}
-template <bool F16>
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    if constexpr (F16)
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-    else
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float swap_pair(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-}
-template <bool X3>
-__device__ __forceinline__ int phys_col(int c) {
-    return X3 ? ((c >> 5) << 6) + (c & 31) : c;
-}
-// one LDS-DMA piece: lane l's 16 bytes at rsrc + voff land at LDS byte lds_addr + 16 l (zeros if voff is out of range)
-__device__ __forceinline__ void dma_piece(unsigned voff, const __amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr) {
-    const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, 0 offen lds" ::"v"(voff), "s"(m0v), "s"(rsrc) : "memory");
-}
 
 template <int MT, int NT, bool F16, bool X3>
 __global__ __launch_bounds__(kThreads, 1) void conv_wres_h16_kernel(const WresArgs a) {
@@ -209,9 +166,8 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wres_h16_kernel(const WresAr
 
     // ---- epilogue (conv_ring_h16.hip's: bias + ReLU + MaxPool in registers, packed rows through a wave-private LDS image,
     // 16-byte stores); the image lives in the slab the tile has just finished with ------------------------------------
-    constexpr int PW = X3 ? 4 : 2;
-    constexpr int PITCH = NT * PW * 16 + 16;
-    constexpr int NPIECE = 8 * NT * PW;
+    using Epi = EpiImage<NT, X3>;
+    constexpr int PW = Epi::PW, PITCH = Epi::PITCH, NPIECE = Epi::NPIECE;
     constexpr int NSTORE = MT * ((NPIECE + 63) / 64) + (X3 ? MT : 0);   // vector stores of one epilogue per wave
     static_assert(8 * (8 * PITCH) <= XS, "epilogue scratch fits the activation slab");
     auto epilogue = [&](int mm0, int cb, int xb) {
@@ -237,18 +193,10 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wres_h16_kernel(const WresAr
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const float us = a.unscale;
-                const float v0 = fmaxf(fmaxf(fmaf(acc[i][j][0], us, bias[j]), fmaf(acc[i][j][1], us, bias[j])), 0.0f);
-                const float v1 = fmaxf(fmaxf(fmaf(acc[i][j][2], us, bias[j]), fmaf(acc[i][j][3], us, bias[j])), 0.0f);
-                const float got = swap_pair(odd ? v0 : v1);
-                const float ca = odd ? got : v0, cb_ = odd ? v1 : got;
-                const unsigned hi = pack2<F16>(ca, cb_);
-                if constexpr (F16) sat |= f16_overflow_bits(hi);
+                const u32x2 hl = pool_pack_pair<F16, X3>(acc[i][j], a.unscale, bias[j], odd, keep, sat);
                 unsigned char* dst = scr + (2 * g + (odd ? 1 : 0)) * PITCH + j * PW * 16 + (r & ~1) * 2;
-                *reinterpret_cast<unsigned*>(dst) = hi & keep;
-                if constexpr (X3)
-                    *reinterpret_cast<unsigned*>(dst + 32) = keep &
-                        pack2<F16>(ca - widen16<F16>((unsigned short)(hi & 0xffffu)), cb_ - widen16<F16>((unsigned short)(hi >> 16)));
+                *reinterpret_cast<unsigned*>(dst) = hl[0];
+                if constexpr (X3) *reinterpret_cast<unsigned*>(dst + 32) = hl[1];
                 acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
