@@ -564,6 +564,31 @@ typedef struct rs_gconv_x3_plan {
  * >= c_in or the column >= c_out.  Needs no device.  RS_ERR_ARG for what rs_gconv_set_mode refuses and for c_in <= 4. */
 RS_API int rs_gconv_x3_layout(int c_in, int c_out, int k, rs_gconv_x3_plan* out, const float* w, uint16_t* packed);
 
+/* Added after ABI 2.9 (rs_version stays 2.9): poly(A) START and END at any window size and MAD threshold - the window rule of
+ * the reference's offline evaluation script (riser/test.py:80-117), which takes both from its command line; rs_polya_end is
+ * the live rule (riser/preprocess.py:42-79) with 500 and 20 built in, and returns the end alone.  With R = resolution, for
+ * window w = 0, 1, ... while (w + 1) R <= len, i = w R:
+ *   - median and MAD of the window's R samples (an even R: the mean of the two middle values, for both); mean of the window;
+ *     rolling = the mean of the 2 R samples before i when i > 2 R (strictly), else the window's own mean;
+ *     change = (mean - rolling) / rolling * 100 in float64 - a zero or negative rolling mean takes no special path, inf and
+ *     nan compare as IEEE does;
+ *   - no start yet, change > 20 and MAD <= mad_threshold: start = i;
+ *   - a start, no end yet and MAD > 20 (a literal, NOT the threshold): end = i - in the start's own window where
+ *     mad_threshold > 20.
+ * d_start / d_end: int32 [B], -1 where the script returns None; a start without an end is (start, -1).  Sums, twice the
+ * median and four times the MAD are integers, so the results equal the reference's for every input.  A read's result never
+ * depends on its batch.  Nothing outside [d_off[b], d_off[b] + min(d_len[b], max_len)) is read: a d_len beyond max_len is
+ * scanned as max_len, a d_len <= 0 gives (-1, -1).  At (500, 20) d_end equals rs_polya_end's.
+ * d_ws: rs_polya_coords_workspace_bytes(B, max_len, resolution) bytes (a table of B x (max_len / resolution) windows), never
+ * assumed clean; the function returns 0 for B <= 0 or arguments rs_polya_coords refuses.
+ * Refused before any device call: resolution outside [1, 16384] (one window and its histogram are staged in a wave's share
+ * of LDS), negative B or max_len, null pointers with B > 0 -> RS_ERR_ARG; a workspace that is too small -> RS_ERR_WORKSPACE.
+ * B == 0 is RS_OK.  Any int32 mad_threshold is accepted (a negative one never starts). */
+RS_API size_t rs_polya_coords_workspace_bytes(int B, int max_len, int resolution);
+RS_API int rs_polya_coords(const int16_t* d_sig, const int64_t* d_off, const int32_t* d_len, int B, int max_len,
+                           int resolution, int mad_threshold, int32_t* d_start, int32_t* d_end,
+                           void* d_ws, size_t ws_bytes, void* stream);
+
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag

@@ -32,6 +32,7 @@ SYMBOLS = (
     "rs_crnn_forward_ragged", "rs_crnn_set_mode",
     "rs_gconv_create", "rs_gconv_destroy", "rs_gconv_min_length", "rs_gconv_max_batch", "rs_gconv_workspace_bytes",
     "rs_gconv_forward_ragged", "rs_gconv_layer_plan", "rs_gconv_set_mode", "rs_gconv_x3_layout",
+    "rs_polya_coords_workspace_bytes", "rs_polya_coords",
 )
 
 
@@ -195,6 +196,10 @@ def lib():
     L.rs_gconv_set_mode.argtypes = [vp, i32]
     L.rs_gconv_x3_layout.restype = i32
     L.rs_gconv_x3_layout.argtypes = [i32, i32, i32, C.POINTER(GConvX3Plan), vp, vp]
+    L.rs_polya_coords_workspace_bytes.restype = sz
+    L.rs_polya_coords_workspace_bytes.argtypes = [i32, i32, i32]
+    L.rs_polya_coords.restype = i32
+    L.rs_polya_coords.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32

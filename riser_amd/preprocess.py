@@ -6,6 +6,8 @@ The median / MAD selection, the normalisation, the outlier smoothing and the pol
 window scan run in HIP kernels (riser_amd/csrc/normalise.hip, polya.hip) through the C
 ABI; results are bit-identical to the reference's float64 numpy path.  Batched variants
 (`mad_normalise_batch`, `get_polyA_end_batch`) are what the batched control loop uses.
+`get_polyA_coords*` is the window rule of the offline evaluation script (riser/test.py:80-117: any
+window size and MAD threshold, start and end; csrc/polya_coords.hip), which riser_amd.evaluate uses.
 """
 from __future__ import annotations
 
@@ -123,6 +125,37 @@ class SignalProcessor:
                                               out.data_ptr(), state_out.data_ptr(),
                                               torch.cuda.current_stream(self.device).cuda_stream), "rs_polya_end_resume")
         return out, state_out
+
+    # ---- poly(A) at any window size and MAD threshold (riser/test.py:80-117) -------------
+    def get_polyA_coords(self, signal, resolution, mad_threshold):
+        """-> (start | None, end | None), the offline evaluation script's window rule."""
+        start, end = self.get_polyA_coords_batch([signal], resolution, mad_threshold)
+        return (None if start[0] < 0 else int(start[0])), (None if end[0] < 0 else int(end[0]))
+
+    def get_polyA_coords_batch(self, signals, resolution, mad_threshold):
+        """-> (starts, ends), int32 [B] each, -1 where the script returns None."""
+        if len(signals) == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        sig, off, ln, lens = pack_reads(signals, self.device)
+        start, end = self.polyA_coords_device(sig, off, ln, len(signals), int(lens.max()), resolution, mad_threshold)
+        return start.cpu().numpy(), end.cpu().numpy()
+
+    def polyA_coords_device(self, sig, off, ln, B, max_len, resolution, mad_threshold):
+        """Raw reads on the device -> (starts, ends), int32 [B] on the device (-1: none); reads longer than `max_len` are
+        scanned as their first `max_len` samples (rs_polya_coords)."""
+        B, max_len, resolution, mad_threshold = int(B), int(max_len), int(resolution), int(mad_threshold)
+        start = torch.empty(B, dtype=torch.int32, device=self.device)
+        end = torch.empty(B, dtype=torch.int32, device=self.device)
+        L = nv.lib()
+        need = int(L.rs_polya_coords_workspace_bytes(B, max_len, resolution))
+        # the launches are asynchronous: the window table belongs to the processor, not to this frame, and only grows
+        ws = self.__dict__.get("_coords_ws")
+        if ws is None or ws.numel() < need:
+            ws = self._coords_ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        nv.check(L.rs_polya_coords(sig.data_ptr(), off.data_ptr(), ln.data_ptr(), B, max_len, resolution, mad_threshold,
+                                   start.data_ptr(), end.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   torch.cuda.current_stream(self.device).cuda_stream), "rs_polya_coords")
+        return start, end
 
     def trim_polyA(self, signal, read_id, cache):
         """-> (signal without adapter + poly(A), True) when a poly(A) end is known for the read, else (signal, False)
