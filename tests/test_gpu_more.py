@@ -735,23 +735,25 @@ def test_other_channel_widths_all_modes(dev, channels):
     """ConvNets of the shipped class (depth 1, kernel 3, gap_fc) with OTHER channel widths: every width class of the
     streaming kernels (layer 1 with 17..32 channels, layer 2 with one, two or three 16-channel tiles, layer 0 below 20
     channels), the tiled kernels on odd widths, 3- to 6-layer nets; fp32, plain 16-bit and split precision against the
-    oracle on a mixed-length batch, and the one-launch streaming form against the two-launch one bit for bit."""
-    from riser_amd.model import Model
+    oracle on a mixed-length batch (bf16 inside its own envelope, test_gpu_parity.H16_TOL; f16xf8 as planned and with every
+    layer from 64 input channels on in the 8-bit form), and the one-launch streaming form against the two-launch one bit for bit."""
     from riser_amd.preprocess import pack_reads
     from conftest import hooked_model
+    from test_gpu_parity import H16_TOL
     cfg = synth.Config(synth.CnnConfig(channels=list(channels), kernels=[3] * len(channels)))
     sd = synth.make_state_dict(7, channels=channels)
     lens = [4096, 8000, 5000, 8191, 4097, 6024, 7777]
     sigs = [synth.make_signals(SIG_SEED, 1, n, first_read=700 + i)[0] for i, n in enumerate(lens)]
     sig, off, ln, lh = pack_reads(sigs, dev)
     want = ro.classify_reads(sd, sigs)
-    for dtype, tol in (("f32w", 1e-4), ("f32", 1e-4), ("f16x3", 1e-3), ("bf16x3", 1e-3), ("f16", 3e-2)):
-        m = Model(sd, cfg, None, "m", dtype=dtype, device=dev)
+    for dtype, tol, env in (("f32w", 1e-4, {}), ("f32", 1e-4, {}), ("f16x3", 1e-3, {}), ("bf16x3", 1e-3, {}), ("f16", 3e-2, {}),
+                            ("bf16", H16_TOL["bf16"], {}), ("f16xf8", 1e-3, {}), ("f16xf8", 1e-3, {"RS_F8_MIN_CIN": "64"})):
+        m = hooked_model(env, sd, dtype, dev, config=cfg)
         got = m.classify_raw(sig, off, ln, lh).cpu().numpy()
-        assert np.abs(got - want).max() < tol, (dtype, channels, np.abs(got - want).max())
-        if dtype in ("f16x3", "bf16x3", "f16"):
-            m2 = hooked_model({"RS_NO_STREAM012": "1"}, sd, dtype, dev, config=cfg)
-            assert np.array_equal(got, m2.classify_raw(sig, off, ln, lh).cpu().numpy()), (dtype, channels)
+        assert np.abs(got - want).max() < tol, (dtype, env, channels, np.abs(got - want).max())
+        if dtype in ("f16x3", "bf16x3", "f16", "f16xf8"):
+            m2 = hooked_model(dict(env, RS_NO_STREAM012="1"), sd, dtype, dev, config=cfg)
+            assert np.array_equal(got, m2.classify_raw(sig, off, ln, lh).cpu().numpy()), (dtype, env, channels)
             m2.close()
         # batch composition: a sub-batch reproduces its rows bit for bit
         idx = torch.tensor([5, 0, 3], device=dev)
