@@ -589,6 +589,33 @@ RS_API int rs_polya_coords(const int16_t* d_sig, const int64_t* d_off, const int
                            int resolution, int mad_threshold, int32_t* d_start, int32_t* d_end,
                            void* d_ws, size_t ws_bytes, void* stream);
 
+/* Added after ABI 2.9, rs_version unchanged: the reference's retraining preprocessing (riser/retrain/preprocess.py) for a
+ * batch of reads, at up to four prefix lengths in one launch.  For read b and cutoff n = cutoffs[c], unless
+ * d_rows[c * B + b] < 0 or d_len[b] < n (the pair is skipped and nothing is written for it):
+ *   - x[i], i < n: elem_bytes 2 - float32(scale * (float64(raw[i]) + offset)), evaluated in float64 and rounded once, with
+ *     (offset, scale) = d_calib[2 b], d_calib[2 b + 1] and scale = range / digitisation: the numpy expression
+ *     np.array(scale * (raw + offset), dtype=np.float32), which is what the tests pin; it is believed, not verified here, to be
+ *     what ont_fast5_api's get_raw_data(scale=True) evaluates.  elem_bytes 4 - the float32 pA values as given (finite).
+ *   - med = np.median(x) and mad = np.median(|x - med|) in float32 (an even n: (a + b) / 2 of the two middle values; -0.0
+ *     orders below +0.0);
+ *   - y = (x - med) / (float32(1.4826) * mad), one rounding per operation, IEEE division, NO zero-MAD guard (:42-44): a zero
+ *     MAD gives NaN where x == med and +-inf elsewhere - where rs_normalise_float, the live rule, writes zeros;
+ *   - the script's smoothing (:18-33) with lim = outlier_lim as a float32: the outliers are {|y| > lim}, taken once (NaN is
+ *     none, +-inf is one), and are replaced in ascending order in place: index 0 by y[1], index n - 1 by the updated
+ *     y[n - 2], any other by (updated y[i - 1] + original y[i + 1]) / 2 clipped to [-lim, lim] (NaN passes the clip).
+ * The n results go to d_out[c] + d_rows[c * B + b] * n; (median, MAD) as doubles to d_stats[2 (c * B + b)] where d_stats is
+ * given.  Every value equals the reference function's bit for bit, NaN comparing as NaN whatever its sign and payload.  A
+ * read's result depends neither on its batch nor on the other cutoffs, and nothing at or behind sample n influences it; no
+ * sample at or behind the longest cutoff that applies to a read is loaded.
+ * cutoffs and d_out are HOST arrays of n_cut entries; everything else named d_ is device memory.
+ * Refused before any device call with RS_ERR_ARG: elem_bytes other than 2 or 4; n_cut outside [1, 4] or null cutoffs; a
+ * cutoff below 2 (the script indexes arr[1]) or above 32768 (the read is staged in LDS); cutoffs not strictly ascending;
+ * B < 0; outlier_lim not finite or negative; with B > 0 a null d_sig, d_off, d_len, d_rows, d_out or d_out[c], and a null
+ * d_calib with elem_bytes 2.  B == 0 is RS_OK. */
+RS_API int rs_retrain_prepare(const void* d_sig, int elem_bytes, const int64_t* d_off, const int32_t* d_len,
+                              const double* d_calib, int B, const int32_t* cutoffs, int n_cut, float outlier_lim,
+                              const int64_t* d_rows, float* const* d_out, double* d_stats, void* stream);
+
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag

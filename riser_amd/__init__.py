@@ -4,7 +4,7 @@ SignalProcessor.mad_normalise -> Model.classify path and its ReadUntil batching 
 Importing the package does not touch the GPU; constructing Model / SignalProcessor does,
 and raises if the HIP library (riser_amd/lib/libriser_amd.so) or a device is missing.
 """
-__all__ = ["Model", "SignalProcessor", "Kit", "SequencerControl"]
+__all__ = ["Model", "SignalProcessor", "Kit", "SequencerControl", "retrain"]
 
 
 def __getattr__(name):
@@ -17,4 +17,7 @@ def __getattr__(name):
     if name == "SequencerControl":
         from .control import SequencerControl
         return SequencerControl
+    if name == "retrain":
+        import importlib
+        return importlib.import_module(".retrain", __name__)
     raise AttributeError(name)

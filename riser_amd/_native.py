@@ -32,7 +32,7 @@ SYMBOLS = (
     "rs_crnn_forward_ragged", "rs_crnn_set_mode",
     "rs_gconv_create", "rs_gconv_destroy", "rs_gconv_min_length", "rs_gconv_max_batch", "rs_gconv_workspace_bytes",
     "rs_gconv_forward_ragged", "rs_gconv_layer_plan", "rs_gconv_set_mode", "rs_gconv_x3_layout",
-    "rs_polya_coords_workspace_bytes", "rs_polya_coords",
+    "rs_polya_coords_workspace_bytes", "rs_polya_coords", "rs_retrain_prepare",
 )
 
 
@@ -200,6 +200,8 @@ def lib():
     L.rs_polya_coords_workspace_bytes.argtypes = [i32, i32, i32]
     L.rs_polya_coords.restype = i32
     L.rs_polya_coords.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    L.rs_retrain_prepare.restype = i32
+    L.rs_retrain_prepare.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, vp, C.POINTER(vp), vp, vp]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32
