@@ -107,20 +107,23 @@ def mad_normalise(signal: np.ndarray) -> np.ndarray:
     return y
 
 
-def mad_normalise_float(signal: np.ndarray) -> np.ndarray:
+def mad_normalise_float(signal: np.ndarray, lim=OUTLIER_LIMIT, zero_mad_guard: bool = True) -> np.ndarray:
     """riser/preprocess.py:108-147 for float16 / float32 / float64 input (the retrain path's pA-scaled signals,
     riser/retrain/preprocess.py:79).  numpy >= 2 (NEP 50) keeps the array's precision: np.median and np.abs(x - med)
     return the input dtype T, the Python float 1.4826 adopts T in `1.4826 * mad`, so y = (x - med) / (T(1.4826) * mad)
-    and the smoothing recurrence run entirely in T.  mad == 0 gives the int64 zero array of the integer case."""
+    and the smoothing recurrence run entirely in T.  mad == 0 gives the int64 zero array of the integer case.
+    The retraining script's copy of the rule (riser/retrain/preprocess.py:8-44) differs in two things: the limit is an
+    argument, and there is no zero-MAD guard (zero_mad_guard=False: NaN where x == med, +-inf elsewhere; NaN is no outlier
+    and passes the clip)."""
     x = np.asarray(signal)
     T = x.dtype.type
     n = x.shape[0]
     med = np.median(x)
     mad = np.median(np.abs(x - med))
-    if mad == 0:
+    if zero_mad_guard and mad == 0:
         return np.zeros(n, dtype=np.int64)
     y = ((x - med) / (T(SCALING_FACTOR) * mad)).astype(x.dtype)
-    lim = T(OUTLIER_LIMIT)
+    lim = T(lim)
     for i in np.flatnonzero(np.abs(y) > lim):                            # ascending; the set is fixed up front (:129)
         if i == 0:
             y[0] = y[1]
@@ -128,7 +131,7 @@ def mad_normalise_float(signal: np.ndarray) -> np.ndarray:
             y[i] = y[i - 1]
         else:
             v = (y[i - 1] + y[i + 1]) / T(2)
-            y[i] = min(max(v, -lim), lim)
+            y[i] = lim if v > lim else (-lim if v < -lim else v)
     return y
 
 

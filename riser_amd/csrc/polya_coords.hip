@@ -14,6 +14,7 @@
 //      sums of the two windows before it, so 64 windows are judged at once and the first start, then the first end at or
 //      behind it, are picked from a ballot; the float64 expressions keep the reference's operation order (-ffp-contract=off).
 #include "common.hpp"
+#include "signal/wave_rank.hpp"
 
 #include <algorithm>
 
@@ -58,13 +59,7 @@ __device__ __forceinline__ void histogram(const int16_t* S, unsigned* H, int R, 
 // ranks k0 <= k1 among the counted samples -> (bin << 16) | rank inside the bin, for each
 __device__ __forceinline__ void find_ranks(const int (&c)[4], int lane, int k0, int k1, int& r0, int& r1) {
     const int t = c[0] + c[1] + c[2] + c[3];
-    int incl = t;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += v;
-    }
-    int run = incl - t;
+    int run = wave_scan_inclusive(t, lane) - t;
     r0 = -1;
     r1 = -1;
 #pragma unroll

@@ -1,6 +1,6 @@
 // The order-preserving integer image of a floating-point value: key(a) < key(b) as unsigned integers exactly where a < b as
-// floats (-0.0 below +0.0), so that order statistics of floats are found by counting on integer digits (normalise_float.hip,
-// retrain_prep.hip).  kPasses: 8-bit digits per key.
+// floats (-0.0 below +0.0), so that order statistics of floats are found by counting on integer digits
+// (signal/radix_select.hpp).  kPasses: 8-bit digits per key.
 #pragma once
 
 namespace rs {

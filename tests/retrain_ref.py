@@ -1,9 +1,12 @@
 """numpy mirror of the reference's retraining preprocessing (riser/retrain/preprocess.py:8-44) and the reads of
-tests/golden/retrain.npz.  The mirror is float32 throughout, float64 only in the pA scaling; tests/test_retrain_cpu.py pins
-it to the script's own answers, and it is the yardstick for inputs larger than a fixture can hold."""
+tests/golden/retrain.npz.  The rule itself is oracle.riser_oracle.mad_normalise_float without its zero-MAD guard, float32
+throughout; float64 only in the pA scaling.  tests/test_retrain_cpu.py pins the mirror to the script's own answers, and it is
+the yardstick for inputs larger than a fixture can hold."""
 import zlib
 
 import numpy as np
+
+from oracle import riser_oracle as ro
 
 F32 = np.float32
 
@@ -17,21 +20,10 @@ def pa(raw, offset, rng, digitisation):
 def mad_normalise(x, lim):
     """-> (y float32 [n], median, mad): the script's mad_normalise on a float32 signal, no zero-MAD guard"""
     x = np.ascontiguousarray(x, dtype=np.float32)
-    lim = F32(lim)
     med = F32(np.median(x))
-    mad = F32(np.median(np.abs(x - med)))
     with np.errstate(divide="ignore", invalid="ignore"):
-        y = ((x - med) / (F32(1.4826) * mad)).astype(np.float32)
-        n = y.shape[0]
-        for i in np.nonzero(np.abs(y) > lim)[0]:                       # taken once, before any update
-            if i == 0:
-                y[i] = y[1]
-            elif i == n - 1:
-                y[i] = y[i - 1]
-            else:
-                v = F32(F32(y[i - 1] + y[i + 1]) / F32(2))
-                y[i] = lim if v > lim else (-lim if v < -lim else v)
-    return y, med, mad
+        y = ro.mad_normalise_float(x, lim=lim, zero_mad_guard=False)
+    return y, med, F32(np.median(np.abs(x - med)))
 
 
 def prepare(signals_pa, cutoffs, lim):

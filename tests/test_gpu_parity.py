@@ -168,6 +168,49 @@ def test_normalise_float_inputs_golden(proc, golden_dir):
         proc.mad_normalise(np.zeros(0, dtype=np.float32))
 
 
+SMALL_FLOAT_LENGTHS = (2, 3, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1023)
+TIED_ADC = (470, 485, 500, 515, 540)
+
+
+def small_float_reads(dt):
+    """per length a noisy read (mixed sign, an outlier at each end and a run of three where n > 8) and a read of five distinct
+    values: with n / 5 samples on each, the two middle order statistics of an even n are equal, of the values and of their
+    deviations.  Two or three samples with a non-zero MAD are all distinct, so those lengths draw without replacement."""
+    rng = np.random.default_rng(20261019)
+    base, tied = [], []
+    for n in SMALL_FLOAT_LENGTHS:
+        s = 500 + rng.integers(-15, 16, (4, n)).sum(0)
+        if n > 8:
+            s[0], s[n - 1] = 2500, -900
+            s[n // 2: n // 2 + 3] = (2000, -1500, 2200)
+        base.append((s * 0.17548 - 80.0).astype(dt))
+        t = rng.choice(np.array(TIED_ADC), size=n, replace=n > 3)
+        tied.append((t * 0.17548 - 80.0).astype(dt))
+    return base, tied
+
+
+@pytest.mark.parametrize("dt", ["float16", "float32", "float64"])
+def test_normalise_float_small_shapes(proc, dt):
+    """rs_normalise_float below the 3690 samples of the golden cases, where the shared select's wave-level edges sit: partly
+    filled waves, waves without an element, and the next_same / min-reduction branch of an even n; one batch per dtype, each row
+    and its (median, MAD) bit for bit against the oracle and numpy"""
+    base, tied = small_float_reads(dt)
+    for x in tied[3:]:
+        if len(x) % 2 == 0:
+            v = np.sort(x)
+            assert v[len(x) // 2 - 1] == v[len(x) // 2], len(x)
+    reads = base + tied
+    outs, stats = proc.mad_normalise_float_batch(reads, return_stats=True)
+    for x, o, st in zip(reads, outs, stats):
+        med = np.median(x)
+        mad = np.median(np.abs(x - med))
+        assert mad != 0 and np.isfinite(x).all(), len(x)                      # no row takes the int64-zeros path
+        want = ro.mad_normalise(x)
+        assert want.dtype == x.dtype and np.isfinite(want).all(), len(x)
+        assert o.dtype == want.dtype and np.array_equal(o, want), (dt, len(x))
+        assert st[0] == med and st[1] == mad, (dt, len(x), st)
+
+
 # ------------------------------------------------------------------------------------------
 # polyA
 # ------------------------------------------------------------------------------------------
