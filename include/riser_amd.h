@@ -580,7 +580,9 @@ RS_API int rs_gconv_x3_layout(int c_in, int c_out, int k, rs_gconv_x3_plan* out,
  * depends on its batch.  Nothing outside [d_off[b], d_off[b] + min(d_len[b], max_len)) is read: a d_len beyond max_len is
  * scanned as max_len, a d_len <= 0 gives (-1, -1).  At (500, 20) d_end equals rs_polya_end's.
  * d_ws: rs_polya_coords_workspace_bytes(B, max_len, resolution) bytes (a table of B x (max_len / resolution) windows), never
- * assumed clean; the function returns 0 for B <= 0 or arguments rs_polya_coords refuses.
+ * assumed clean; the function returns 0 for B <= 0 or arguments rs_polya_coords refuses.  The table is int32 pairs
+ * [B][max_len / resolution] = (window sum, 4 x MAD); entries of windows a read does not have are not written, nor is any byte
+ * behind the table.
  * Refused before any device call: resolution outside [1, 16384] (one window and its histogram are staged in a wave's share
  * of LDS), negative B or max_len, null pointers with B > 0 -> RS_ERR_ARG; a workspace that is too small -> RS_ERR_WORKSPACE.
  * B == 0 is RS_OK.  Any int32 mad_threshold is accepted (a negative one never starts). */
