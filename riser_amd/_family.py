@@ -7,9 +7,16 @@ its program into rs_<family>_create (`_create`), words its own refusals, and add
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _native as nv
+
+
+def load_state(state) -> dict:
+    """a state dict, or the path of one, as {name: numpy array} on the host; arrays that already are numpy are kept as they are"""
+    sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")              # riser/model.py:19
+    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
 
 
 class FamilyNet:

@@ -14,17 +14,12 @@ from __future__ import annotations
 import ctypes as C
 
 import numpy as np
-import torch
 
 from . import _native as nv
-from ._family import FamilyNet
+from ._family import FamilyNet, load_state
 
 CELLS = {"lstm": 0, "gru": 1}
 GATES = {"lstm": 4, "gru": 3}
-
-
-def _np(sd):
-    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
 
 
 def _get(sd, key):
@@ -37,7 +32,7 @@ def build_crnn_program(sd, c) -> dict:
     """dict(convs=[dict(w [co, ci, k], b, k)], layers=[dict(cell, in_dim, hidden, bidirectional, w_ih, w_hh, b_ih, b_hh
     (lists per direction), relu_after)], fc_w [2, out_dim], fc_b [2], out_dim) of a reference ConvRecNet state dict and its
     `config.cnn_rnn`.  Refuses (ValueError) what the reference cannot run or what does not match the state dict."""
-    sd = _np(sd)
+    sd = load_state(sd)
     cell = str(getattr(c, "cell", "")).lower()
     if cell not in CELLS:
         raise ValueError(f"cell {getattr(c, 'cell', None)!r}: the reference knows 'lstm' and 'gru' (cnn_rnn.py:55-70)")
@@ -147,9 +142,6 @@ class CRNNNet(FamilyNet):
     _MODES = {"f32": ("f32", nv.RS_F32), "f32w": ("f32", nv.RS_F32W), "fp32": ("f32", nv.RS_F32),
               "f16x3": ("f16x3", nv.RS_F16X3)}
 
-    def __init__(self, prog, device, dtype: str = "f32"):
-        super().__init__(prog, device, dtype)
-
     @classmethod
     def _refused_dtype(cls, dtype):
         return (f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'f16x3' (split precision "
@@ -180,6 +172,7 @@ class CRNNNet(FamilyNet):
 
     @property
     def min_length(self) -> int:
+        """shorter: the reference's conv or max_pool raises"""
         return int(nv.lib().rs_crnn_min_length(self._h))
 
     def steps(self, L: int) -> int:

@@ -12,14 +12,9 @@ from __future__ import annotations
 import ctypes as C
 
 import numpy as np
-import torch
 
 from . import _native as nv
-from ._family import FamilyNet
-
-
-def _np(sd):
-    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
+from ._family import FamilyNet, load_state
 
 
 def _get(sd, key):
@@ -45,7 +40,7 @@ def build_gconv_program(sd, cnn) -> dict:
         raise ValueError(f"classifier {classifier!r}: the generic ConvNet family runs the `gap_fc` head only")
     if int(cnn.n_classes) != 2:
         raise ValueError("riser_amd supports two-class heads only")
-    sd = _np(sd)
+    sd = load_state(sd)
     convs, c_in = [], 1
     for i in range(n_layers):
         for d in range(depth):
@@ -117,9 +112,6 @@ class GConvNet(FamilyNet):
     _PREFIX = "rs_gconv"
     _MODES = {"f32": ("f32", nv.RS_F32), "f32w": ("f32", nv.RS_F32W), "fp32": ("f32", nv.RS_F32),
               "bf16x3": ("bf16x3", nv.RS_BF16X3)}
-
-    def __init__(self, prog, device, dtype: str = "f32"):
-        super().__init__(prog, device, dtype)
 
     @classmethod
     def _refused_dtype(cls, dtype):

@@ -7,6 +7,7 @@ through the C ABI; torch is used only for device memory and the current stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -14,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as nv
+from ._family import load_state
 
 _DTYPES = {"f32": nv.RS_F32, "fp32": nv.RS_F32, "float32": nv.RS_F32,
            "bf16": nv.RS_BF16, "bfloat16": nv.RS_BF16, "f16": nv.RS_F16, "fp16": nv.RS_F16,
@@ -33,6 +35,36 @@ def is_half_dtype(dtype: str) -> bool:
 
 def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def select_architecture(config) -> str:
+    """Which of "cnn-rnn", "tcn-bot", "tcn", "resnet", "cnn" a config asks Model for: by its `model`
+    string, else by the section it carries - and a `cnn` section beats every other section.  The first rule that holds
+    decides; an unknown `model` string names nothing, so the sections decide.  Reads attributes only: no torch, no GPU."""
+    kind = getattr(config, "model", None)
+    others = not hasattr(config, "cnn")             # the presence of another section counts only without a `cnn` one
+    if kind == "cnn-rnn" or (kind is None and others and hasattr(config, "cnn_rnn")):
+        return "cnn-rnn"
+    if kind == "resnet" or (others and hasattr(config, "resnet")):
+        return "resnet"
+    if kind == "tcn-bot" or (kind != "tcn" and others and hasattr(config, "tcnbot")):
+        return "tcn-bot"
+    if kind == "tcn" or (others and hasattr(config, "tcn")):
+        return "tcn"
+    return "cnn"
+
+
+def _outputs(device, shape, out=None, return_logits: bool = False):
+    """(probs, logits) of an entry point: the caller's `out` or a new fp32 tensor of `shape`, and logits only when asked for"""
+    probs = out if out is not None else torch.empty(shape, dtype=torch.float32, device=device)
+    return probs, (torch.empty(shape, dtype=torch.float32, device=device) if return_logits else None)
+
+
+def _call_bounds(B: int, mb: int):
+    """[(s0, s1), ...]: the sub-batches a batch of B reads is cut into at mb = Model.call_batch(B, lmax) reads per library call
+    (of an ensemble: its most restrictive model's); empty when one call takes the whole batch.  Reads are independent, so the
+    cut changes nothing but the time."""
+    return [(s0, min(B, s0 + mb)) for s0 in range(0, B, mb)] if B > mb else ()
 
 
 class Workspace:
@@ -67,6 +99,9 @@ class Model:
 
     HALF_MODES = ("f16", "f16x3", "f16xf8")        # activations stored as IEEE half: a range of 65504
     HALF_MAX = 65504.0
+    # present on every Model, whichever arm built it (and on one no arm has built yet: close(), is_half)
+    _h = _seq = _lib_dtype = _canonical = _twin_source = None
+    _fc_positions = _fc_hidden = 0
 
     def __init__(self, state, config, logger, target, dtype: str = "f32w", device=None, range_check: bool = True):
         """dtype: "f32w" (default; fp32 end to end, conv layers as Winograd F(2,3) / F(4,3) on the
@@ -83,47 +118,37 @@ class Model:
         when an activation comes within a factor of 4 of half precision's 65504 - those modes cannot represent larger
         activations, the reference's fp32 path can (riser/model.py:22-28).  RS_RANGE_CHECK=0 or range_check=False skip it;
         at run time `saturated()` (and a warning from `classify`) report an overflow on the real data."""
-        self.target = target
-        self.logger = logger
+        self.target, self.logger = target, logger
         self.device = self._get_device(device)
         if logger is not None:
             logger.info('Using %s device', self.device)
-        kind = getattr(config, "model", None)
-        if kind == "cnn-rnn" or (kind is None and not hasattr(config, "cnn") and hasattr(config, "cnn_rnn")):
-            # `config.cnn_rnn` (riser/nets/cnn_rnn.py:7-33, ConvRecNet): conv front + stacked LSTM / GRU (csrc/crnn.hip).
-            # The reference's train.py has no branch for it; `model: cnn-rnn`, or a config with a `cnn_rnn` section and
-            # neither `model` nor `cnn`, selects it here
-            self._init_crnn(state, config.cnn_rnn, dtype)
-            return
-        is_resnet = kind == "resnet" or (not hasattr(config, "cnn") and hasattr(config, "resnet"))
-        if not is_resnet and (kind == "tcn-bot" or (kind != "tcn" and not hasattr(config, "cnn") and hasattr(config, "tcnbot"))):
-            # `config.tcnbot` (riser/nets/tcn_bot.py:63-85) or `config.tcn` (riser/nets/tcn.py:62-82), what riser/train.py:175-182
-            # trains for `model: tcn-bot` / `tcn`: the receptive cone of the last position (csrc/tcn.hip), behind the same
-            # surface as the ResNet below
-            self._init_tcn(state, config.tcnbot, True, dtype)
-            return
-        if not is_resnet and (kind == "tcn" or (not hasattr(config, "cnn") and hasattr(config, "tcn"))):
-            self._init_tcn(state, config.tcn, False, dtype)
-            return
-        if is_resnet:
-            # `config.resnet` (riser/nets/resnet.py:72-99: channels, kernel, padding, stride, block, n_layers, blocks,
-            # n_classes) instead of `config.cnn`: the reference's second architecture.  Its own Model hard-wires ConvNet
-            # (riser/model.py:13) and ships no ResNet config or weights; here the same Model surface - classify, the batched
-            # entry points, SequencerControl - runs it as a generic conv program (csrc/seqnet.hip: one launch for the stem
-            # and one per residual block), in fp32 or, dtype "bf16x3", with stem and basic blocks on the bf16 MFMA.
-            self._init_resnet(state, config.resnet, dtype)
-            return
+        self.model = self            # the reference exposes the nn.Module here; kept as an alias
+        self._keep, self._cls_slots, self._cls_next = [], [], 0
+        sd = load_state(state)
+        kind = select_architecture(config)
+        if kind == "cnn-rnn":
+            self._init_crnn(sd, config.cnn_rnn, dtype)
+        elif kind == "tcn-bot":
+            self._init_tcn(sd, config.tcnbot, True, dtype)
+        elif kind == "tcn":
+            self._init_tcn(sd, config.tcn, False, dtype)
+        elif kind == "resnet":
+            self._init_resnet(sd, config.resnet, dtype)
+        else:
+            self._init_cnn(sd, config, dtype)
+        if self.is_half and range_check and os.environ.get("RS_RANGE_CHECK", "1") != "0":
+            try:
+                self._half_range_check()
+            except Exception:
+                self.close()
+                raise
+
+    def _init_cnn(self, sd, config, dtype: str):
         cnn = config.cnn
         self.classifier = getattr(cnn, "classifier", "gap_fc")
         if self.classifier not in ("gap_fc", "gap", "fc"):
             raise ValueError(f"classifier {self.classifier!r}: the reference knows `fc`, `gap_fc` and `gap` "
                              "(riser/nets/cnn.py:21-41)")
-        self._fc_positions = 0
-        if isinstance(state, dict):
-            sd = state
-        else:
-            sd = torch.load(state, map_location="cpu")              # riser/model.py:19
-        sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
         if self.classifier == "gap":
             # Conv1d(C, n_classes, 1) then the mean over positions (riser/nets/cnn.py:34-38) = the mean, then the same
             # matrix: W mean_p(x_p) + b.  Runs as the gap_fc head with the 1 x 1 kernel read as a matrix (fp32 summation
@@ -135,13 +160,14 @@ class Model:
             sd["classifier.2.bias"] = np.asarray(sd["classifier.0.bias"])
         self.channels = [int(c) for c in cnn.channels][: int(cnn.n_layers)]
         self.n_layers = len(self.channels)
+        kernels = [int(k) for k in list(cnn.kernels)[: self.n_layers]]
+        shipped = int(getattr(cnn, "depth", 1)) == 1 and all(k == 3 for k in kernels)
         fc = None
         if self.classifier == "fc":
             # Flatten -> Linear(C * P, H) -> ReLU -> Linear(H, n_classes) (riser/nets/cnn.py:22-27; the reference hard-codes
             # C * P = 67 * 753 and H = 4096: one input length of one 4-layer net).  Runs behind the conv stack as two extra
             # kernels (csrc/fc_head.hip); the gap_fc weights the library is created with are placeholders.
-            if int(getattr(cnn, "depth", 1)) != 1 or any(int(k) != 3 for k in list(cnn.kernels)[: self.n_layers]) \
-                    or dtype not in ("f32w", "f32"):
+            if not shipped or dtype not in ("f32w", "f32"):
                 raise ValueError("the `fc` classifier runs behind the depth-1, kernel-3 conv stack in fp32 (dtype f32w / f32)")
             w1 = np.ascontiguousarray(sd["classifier.1.weight"], dtype=np.float32)
             c_last = self.channels[-1]
@@ -155,21 +181,14 @@ class Model:
                 raise ValueError("classifier.1 / classifier.3 shapes do not match each other or n_classes")
             sd["classifier.2.weight"] = np.zeros((int(cnn.n_classes), c_last), dtype=np.float32)
             sd["classifier.2.bias"] = np.zeros(int(cnn.n_classes), dtype=np.float32)
-        self.min_length = 1 << self.n_layers
-        self.dtype = dtype                     # the caller's spelling; _canonical is what tables are keyed by
-        self._canonical = _CANONICAL.get(_DTYPES.get(dtype), dtype)
-        self._keep = []
-        self._seq = None
-        self.model = self            # the reference exposes the nn.Module here; kept as an alias
-        if int(getattr(cnn, "depth", 1)) != 1 or any(int(k) != 3 for k in list(cnn.kernels)[: self.n_layers]):
+        if not shipped:
             # outside the shipped class (depth > 1 or kernels other than 3, riser/nets/cnn.py:17,52-65).  With the `gap_fc`
             # head: the generic ConvNet family of csrc/gconv.hip (tiled conv + ReLU + pool launches, reads of any length in
             # one call).  RS_GCONV=0 or RS_SEQ_SCALAR=1 in the environment now, and the `gap` head, keep the conv / max-pool
             # program of csrc/seqnet.hip (reads grouped by length)
             if int(cnn.n_classes) != 2:
                 raise ValueError("riser_amd supports two-class heads only")
-            self._h = None
-            if any(int(k) % 2 == 0 for k in list(cnn.kernels)[: self.n_layers]):
+            if any(k % 2 == 0 for k in kernels):
                 raise ValueError("riser_amd: even conv kernels ('same' pads them asymmetrically) are not supported")
             family = self.classifier == "gap_fc" and os.environ.get("RS_GCONV", "1") != "0" and "RS_SEQ_SCALAR" not in os.environ
             if dtype not in ("f32w", "f32") and not (family and dtype == "bf16x3"):
@@ -178,14 +197,18 @@ class Model:
                                  "csrc/gconv.hip, in 'bf16x3'")
             if family:
                 from .gconv import GConvNet, build_gconv_program
-                self._seq = GConvNet(build_gconv_program(sd, cnn), device=self.device, dtype=dtype)
-                self.dtype = self._seq.dtype
+                net = GConvNet(build_gconv_program(sd, cnn), device=self.device, dtype=dtype)
             else:
                 from .resnet import SeqNet, build_convnet_program
-                self._seq = SeqNet(*build_convnet_program(sd, cnn), device=self.device)
-                self.dtype = "f32"
-            self._ws = Workspace(self.device)
+                net = SeqNet(*build_convnet_program(sd, cnn), device=self.device)      # its default dtype: "f32"
+            head = self.classifier
+            self._adopt_family(net, self.channels)
+            # as this arm always reported: the config's head (`gap` runs as gap_fc above), the reference's minimum length
+            self.classifier, self.min_length = head, 1 << self.n_layers
             return
+        self.min_length = 1 << self.n_layers
+        self.dtype = dtype                    # the caller's spelling; _canonical is what tables are keyed by
+        self._canonical = _CANONICAL.get(_DTYPES.get(dtype), dtype)
         conv_w, conv_b = [], []
         c_in = 1
         for i, c_out in enumerate(self.channels):
@@ -219,12 +242,6 @@ class Model:
             nv.check(L.rs_model_set_fc_classifier(h, positions, int(w1.shape[0]), w1.ctypes.data, b1.ctypes.data,
                                                   w2.ctypes.data, b2.ctypes.data), "rs_model_set_fc_classifier")
             self._fc_positions, self._fc_hidden = positions, int(w1.shape[0])
-        if self.is_half and range_check and os.environ.get("RS_RANGE_CHECK", "1") != "0":
-            try:
-                self._half_range_check()
-            except Exception:
-                self.close()
-                raise
 
     # ---- half precision's range ----------------------------------------------------------
     @property
@@ -232,7 +249,7 @@ class Model:
         """this model runs a library mode that stores activations as IEEE half (a range of 65504) and carries the overflow
         flag: the shipped ConvNet family in f16 / f16x3 / f16xf8, under any spelling of those names.  False for every other
         mode, the generic programs and the CNN-RNN's f16x3 (bounded operands, no flag)."""
-        return getattr(self, "_lib_dtype", None) in _HALF_LIB_DTYPES
+        return self._lib_dtype in _HALF_LIB_DTYPES
 
     def fp32_range_twin(self) -> "Model":
         """A `bf16x3` Model of the same weights, target and device: fp32's exponent range (its saturated() is always False),
@@ -254,16 +271,14 @@ class Model:
         self._need_handle("half_activation_maxima")
         if signals is None:
             signals = [synth.make_raw_read(4242, rid, 2048 + 8615 + 37 * rid, polya=bool(rid % 5))[2048:] for rid in range(16)]
-        lens = [len(s) for s in signals]
         sig, off, ln, lh = pack_reads(list(signals), self.device)
-        info, out, L = self.layer_info(), [], nv.lib()
+        out = []
         try:
             for i in range(1, self.n_layers):
-                U, bases = self.block_samples(i), self.block_bases(lens, i)
-                rows, cp, fmt = int(bases[-1]) * (U >> (i + 1)), info[i]["cp_out"], info[i]["rows_format"]
+                rows, cp, fmt = self.layer_rows(lh, i)
                 cap = torch.zeros(rows * cp, dtype=torch.float16, device=self.device)
-                nv.check(L.rs_debug_capture_layer(self._h, i, cap.data_ptr(), cap.numel() * 2), "rs_debug_capture_layer")
-                self.classify_raw(sig, off, ln, lh)
+                with self.capture_layer(i, cap):
+                    self.classify_raw(sig, off, ln, lh)
                 v = cap.view(rows, cp)
                 if fmt == 1:
                     v = v.view(rows, cp // 64, 2, 32)[:, :, 0, :]            # [hi x 32 | lo x 32]
@@ -272,7 +287,6 @@ class Model:
                 v = v.float().abs()
                 out.append(float("inf") if not torch.isfinite(v).all() else float(v.max().item()))
         finally:
-            L.rs_debug_capture_layer(self._h, -1, None, 0)
             self.saturated(reset=True)
         return out
 
@@ -321,71 +335,58 @@ class Model:
         d = torch.device(device)
         return torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
 
-    def _init_resnet(self, state, rc, dtype: str):
+    def _adopt_family(self, net, channels):
+        """the common end of every family-backed arm: `net` (any FamilyNet) becomes `_seq`, and the
+        attributes the entry points read are filled from it"""
+        self.classifier, self._fc_positions = "gap_fc", 0
+        self.channels, self.n_layers = channels, len(channels)
+        self._seq = net
+        self.dtype = net.dtype
+        self.min_length = net.min_length
+        self._ws = Workspace(self.device)
+
+    def _init_resnet(self, sd, rc, dtype: str):
+        # `config.resnet` (riser/nets/resnet.py:72-99: channels, kernel, padding, stride, block, n_layers, blocks,
+        # n_classes) instead of `config.cnn`: the reference's second architecture.  Its own Model hard-wires ConvNet
+        # (riser/model.py:13) and ships no ResNet config or weights; here the same Model surface - classify, the batched
+        # entry points, SequencerControl - runs it as a generic conv program (csrc/seqnet.hip: one launch for the stem
+        # and one per residual block), in fp32 or, dtype "bf16x3", with stem and basic blocks on the bf16 MFMA.
         from .resnet import SeqNet, build_program
-        sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
-        sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
         if int(rc.n_classes) != 2:
             raise ValueError("riser_amd supports two-class heads only")
         seq_dtype = {"f32w": "f32", "f32": "f32", "bf16x3": "bf16x3"}.get(dtype)
         if seq_dtype is None:
             raise ValueError(f"dtype {dtype!r}: a ResNet runs in 'f32w' / 'f32' (f32-input MFMA) or 'bf16x3' (stem and basic "
                              "blocks in split precision on the bf16 MFMA)")
-        self.classifier, self._fc_positions = "gap_fc", 0
-        self.channels = [int(c) for c in rc.channels]
-        self.n_layers = len(self.channels)
-        self._keep, self._h, self.model = [], None, self
-        self._seq = SeqNet(*build_program(sd, rc), device=self.device, dtype=seq_dtype)
-        self.dtype = seq_dtype
-        self._ws = Workspace(self.device)
-        # shortest input the program accepts (torch raises below it: kernel larger than the padded input, empty pooling)
-        lo, hi = 1, 1 << 16
-        lib = nv.lib()
-        while lo < hi:
-            mid = (lo + hi) // 2
-            if lib.rs_seqnet_workspace_bytes(self._seq._h, 1, mid):
-                hi = mid
-            else:
-                lo = mid + 1
-        self.min_length = lo
+        self._adopt_family(SeqNet(*build_program(sd, rc), device=self.device, dtype=seq_dtype), [int(c) for c in rc.channels])
 
-    def _init_tcn(self, state, tc, bottleneck: bool, dtype: str):
+    def _init_tcn(self, sd, tc, bottleneck: bool, dtype: str):
+        # `config.tcnbot` (riser/nets/tcn_bot.py:63-85) or `config.tcn` (riser/nets/tcn.py:62-82), what riser/train.py:175-182
+        # trains for `model: tcn-bot` / `tcn`: the receptive cone of the last position (csrc/tcn.hip), behind the same
+        # surface as the ResNet above
         from .tcn import TCNNet, build_tcn_program
         if dtype not in ("f32w", "f32", "bf16x3"):
             raise ValueError(f"dtype {dtype!r}: a TCN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'bf16x3' (split "
                              "precision on the bf16 MFMA)")
-        sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
         blocks, fw, fb = build_tcn_program(sd, tc, bottleneck)
-        self.classifier, self._fc_positions = "gap_fc", 0
-        self.channels = [int(tc.n_filters)] * int(tc.n_layers)
-        self.n_layers = len(self.channels)
-        self._keep, self._h, self.model = [], None, self
-        self._seq = TCNNet(blocks, fw, fb, device=self.device, dtype=dtype)
-        self.dtype = self._seq.dtype
-        self._ws = Workspace(self.device)
-        self.min_length = 1                 # causal convs: any read of one sample or more has a last position
+        self._adopt_family(TCNNet(blocks, fw, fb, device=self.device, dtype=dtype), [int(tc.n_filters)] * int(tc.n_layers))
 
-    def _init_crnn(self, state, cc, dtype: str):
+    def _init_crnn(self, sd, cc, dtype: str):
+        # `config.cnn_rnn` (riser/nets/cnn_rnn.py:7-33, ConvRecNet): conv front + stacked LSTM / GRU (csrc/crnn.hip).
+        # The reference's train.py has no branch for it; `model: cnn-rnn`, or a config with a `cnn_rnn` section and
+        # neither `model` nor `cnn`, selects it
         from .crnn import CRNNNet, build_crnn_program
         if dtype not in ("f32w", "f32", "f16x3"):
             raise ValueError(f"dtype {dtype!r}: a CNN-RNN runs in 'f32w' / 'f32' (fp32 on the f32-input MFMA) or 'f16x3' "
                              "(split precision on the f16 MFMA for the gate GEMMs of hidden states)")
-        sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
         prog = build_crnn_program(sd, cc)
-        self.classifier, self._fc_positions = "gap_fc", 0
-        self.channels = [int(cv["w"].shape[0]) for cv in prog["convs"]]
-        self.n_layers = len(self.channels)
-        self._keep, self._h, self.model = [], None, self
-        self._seq = CRNNNet(prog, device=self.device, dtype=dtype)
-        self.dtype = self._seq.dtype
-        self._ws = Workspace(self.device)
-        self.min_length = self._seq.min_length      # shorter: the reference's conv or max_pool raises
+        self._adopt_family(CRNNNet(prog, device=self.device, dtype=dtype), [int(cv["w"].shape[0]) for cv in prog["convs"]])
 
     def close(self):
-        h, self._h = getattr(self, "_h", None), None
+        h, self._h = self._h, None
         if h:
             nv.lib().rs_model_destroy(h)
-        seq, self._seq = getattr(self, "_seq", None), None
+        seq, self._seq = self._seq, None
         if seq is not None:
             seq.close()
 
@@ -394,12 +395,11 @@ class Model:
         (rs_seqnet_forward_ragged: every kernel masks by the read's own rows); any other program runs one uniform length per
         launch, so its reads are grouped by length"""
         B = x.shape[0]
-        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
         if self._seq.ragged_ok and x.is_contiguous():
             if lens_dev is None:
                 lens_dev = torch.from_numpy(np.ascontiguousarray(lens_host, dtype=np.int32)).to(self.device)
-            return self._seq.forward_ragged(x, lens_dev.to(torch.int32), return_logits, out=probs)
-        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
+            return self._seq.forward_ragged(x, lens_dev.to(torch.int32), return_logits, out=out)
+        probs, logits = _outputs(self.device, (B, 2), out, return_logits)
         for L in np.unique(lens_host):
             idx = torch.from_numpy(np.flatnonzero(lens_host == L)).to(self.device)
             r = self._seq.forward(x[idx, : int(L)].contiguous(), return_logits)
@@ -447,6 +447,28 @@ class Model:
             out.append({n: getattr(li, n) for n, _ in nv.LayerInfo._fields_})
         return out
 
+    def layer_rows(self, lens_host, layer: int):
+        """-> (rows, cp_out, rows_format) of conv layer `layer`'s output buffer for a batch of these lengths: every block of
+        the packed layout (block_bases) holds U >> (layer + 1) rows of cp_out padded channels, in the layer's row format
+        (rs_layer_info).  What a capture_layer buffer is sized and decoded by."""
+        info = self.layer_info()[layer]
+        rows = int(self.block_bases(lens_host, layer)[-1]) * (info["block_samples"] >> (layer + 1))
+        return rows, info["cp_out"], info["rows_format"]
+
+    @contextlib.contextmanager
+    def capture_layer(self, layer: int, buf: torch.Tensor):
+        """Inside the block, every call on this model copies conv layer `layer`'s output buffer, as the device laid it out,
+        into the device tensor `buf` (any dtype: the library is told its size in bytes and copies no more).  The hook is
+        switched off on the way out, whatever happened inside: the library never keeps a pointer to a tensor that may be freed."""
+        self._need_handle("capture_layer")
+        hook = nv.lib().rs_debug_capture_layer
+        nv.check(hook(self._h, int(layer), buf.data_ptr(), buf.numel() * buf.element_size()), "rs_debug_capture_layer")
+        try:
+            yield buf
+        finally:
+            if self._h:
+                hook(self._h, -1, None, 0)
+
     def profile(self, on, coarse: bool = False):
         """HIP-event stage timing on the launch stream; coarse = only the conv stack's boundaries (4 events per call)."""
         self._need_handle("profile")
@@ -481,7 +503,7 @@ class Model:
         hard = self.max_batch(lmax)
         cap = hard
         if self._seq is None:
-            cap = min(hard, max(512, self._CALL_SAMPLES.get(getattr(self, "_canonical", self.dtype), 2048 << 14) // ((int(lmax) // 1024 + 1) * 1024)))
+            cap = min(hard, max(512, self._CALL_SAMPLES.get(self._canonical, 2048 << 14) // ((int(lmax) // 1024 + 1) * 1024)))
         if B <= cap or B <= min(hard, cap + cap // 4):          # the cache-friendly size is a preference: no sliver calls
             return B
         n = -(-B // cap)
@@ -546,8 +568,7 @@ class Model:
 
     def _classify_slot(self, n: int):
         """pinned staging for classify(): four slots used in turn, each with an event that says its last copies are done"""
-        slots = self.__dict__.setdefault("_cls_slots", [])
-        k = self.__dict__.get("_cls_next", 0)
+        slots, k = self._cls_slots, self._cls_next
         self._cls_next = (k + 1) & 3
         if len(slots) <= k:
             slots.append({"x": torch.empty(max(n, 16384), dtype=torch.float32).pin_memory(),
@@ -589,29 +610,29 @@ class Model:
             raise ValueError("a length exceeds the row pitch")
         if self._seq is not None:
             return self._seq_forward(x, np.asarray(lens_host), return_logits, out, lens_dev)
-        mb = self.call_batch(B, lmax)
-        if B > mb:                                                     # split: reads are independent
-            probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-            logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-            for s0 in range(0, B, mb):
-                s1 = min(B, s0 + mb)
-                r = self.forward_batch(x[s0:s1], lens_host[s0:s1], None if lens_dev is None else lens_dev[s0:s1],
-                                       return_logits, out=probs[s0:s1])
-                if return_logits:
-                    logits[s0:s1] = r[1]
-            return (probs, logits) if return_logits else probs
+        parts = _call_bounds(B, self.call_batch(B, lmax))
+        if parts:
+            return self._in_parts(parts, B, out, return_logits, lambda s0, s1, o: self.forward_batch(
+                x[s0:s1], lens_host[s0:s1], None if lens_dev is None else lens_dev[s0:s1], return_logits, out=o))
         lens_host = np.ascontiguousarray(lens_host, dtype=np.int32)
         if lens_dev is None:
             lens_dev = torch.from_numpy(lens_host).to(self.device)
         L = nv.lib()
-        need = L.rs_workspace_bytes(self._h, B, lmax)
-        ws = self._ws.get(need)
-        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
+        ws = self._ws.get(L.rs_workspace_bytes(self._h, B, lmax))
+        probs, logits = _outputs(self.device, (B, 2), out, return_logits)
         nv.check(L.rs_forward(self._h, x.data_ptr(), ldx, lens_dev.data_ptr(), lens_host.ctypes.data, B,
                               int(lens_host.min()), lmax, ws.data_ptr(),
                               ws.numel(), probs.data_ptr(), logits.data_ptr() if return_logits else None,
                               _stream_ptr(self.device)), "rs_forward")
+        return (probs, logits) if return_logits else probs
+
+    def _in_parts(self, parts, B: int, out, return_logits: bool, call):
+        """a batch beyond one library call: call(s0, s1, out=probs[s0:s1]) on each of _call_bounds' parts"""
+        probs, logits = _outputs(self.device, (B, 2), out, return_logits)
+        for s0, s1 in parts:
+            r = call(s0, s1, probs[s0:s1])
+            if return_logits:
+                logits[s0:s1] = r[1]
         return (probs, logits) if return_logits else probs
 
     def classify_raw(self, sig_dev: torch.Tensor, off_dev: torch.Tensor, len_dev: torch.Tensor,
@@ -629,23 +650,14 @@ class Model:
                                            xn.data_ptr(), lmax, lmax, None, 0, None, _stream_ptr(self.device)),
                      "rs_normalise")
             return self._seq_forward(xn, np.asarray(lens_host), return_logits, out, len_dev)
-        mb = self.call_batch(B, lmax)
-        if B > mb:                                                     # split: reads are independent
-            probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-            logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
-            for s0 in range(0, B, mb):
-                s1 = min(B, s0 + mb)
-                r = self.classify_raw(sig_dev, off_dev[s0:s1], len_dev[s0:s1], lens_host[s0:s1], out=probs[s0:s1],
-                                      return_logits=return_logits, packed=packed)
-                if return_logits:
-                    logits[s0:s1] = r[1]
-            return (probs, logits) if return_logits else probs
+        parts = _call_bounds(B, self.call_batch(B, lmax))
+        if parts:
+            return self._in_parts(parts, B, out, return_logits, lambda s0, s1, o: self.classify_raw(
+                sig_dev, off_dev[s0:s1], len_dev[s0:s1], lens_host[s0:s1], out=o, return_logits=return_logits, packed=packed))
         L = nv.lib()
         lens_host = np.ascontiguousarray(lens_host, dtype=np.int32)
-        need = L.rs_workspace_bytes(self._h, B, lmax)
-        ws = self._ws.get(need)
-        probs = out if out is not None else torch.empty((B, 2), dtype=torch.float32, device=self.device)
-        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device) if return_logits else None
+        ws = self._ws.get(L.rs_workspace_bytes(self._h, B, lmax))
+        probs, logits = _outputs(self.device, (B, 2), out, return_logits)
         nv.check(L.rs_classify(self._h, sig_dev.data_ptr(), off_dev.data_ptr(), len_dev.data_ptr(),
                                lens_host.ctypes.data if packed else None, B, int(lens_host.min()), lmax,
                                ws.data_ptr(), ws.numel(), probs.data_ptr(),
@@ -653,28 +665,24 @@ class Model:
                  "rs_classify")
         return (probs, logits) if return_logits else probs
 
-
-def _autotune(self, sig_dev: torch.Tensor, off_dev: torch.Tensor, len_dev: torch.Tensor, lens_host: np.ndarray) -> int:
-    """Time every feasible tile shape of each tiled conv layer on this batch (rs_autotune) and keep the measured best
-    for later batches of the same geometry; returns the number of layers whose choice changed.  Optional: call once per
-    deployment batch size (e.g. before a run); results are bit-identical with or without it."""
-    self._need_handle("autotune")
-    self._check_lengths(lens_host)
-    B, lmax = int(lens_host.shape[0]), int(lens_host.max())
-    if B > self.max_batch(lmax):
-        raise ValueError("autotune: batch exceeds one library call (Model.max_batch)")
-    lens_host = np.ascontiguousarray(lens_host, dtype=np.int32)
-    L = nv.lib()
-    ws = self._ws.get(L.rs_workspace_bytes(self._h, B, lmax))
-    probs = torch.empty((B, 2), dtype=torch.float32, device=self.device)
-    changed = C.c_int32(0)
-    nv.check(L.rs_autotune(self._h, sig_dev.data_ptr(), off_dev.data_ptr(), len_dev.data_ptr(), lens_host.ctypes.data, B,
-                           int(lens_host.min()), lmax, ws.data_ptr(), ws.numel(), probs.data_ptr(), C.byref(changed), _stream_ptr(self.device)),
-             "rs_autotune")
-    return changed.value
-
-
-Model.autotune = _autotune
+    def autotune(self, sig_dev: torch.Tensor, off_dev: torch.Tensor, len_dev: torch.Tensor, lens_host: np.ndarray) -> int:
+        """Time every feasible tile shape of each tiled conv layer on this batch (rs_autotune) and keep the measured best
+        for later batches of the same geometry; returns the number of layers whose choice changed.  Optional: call once per
+        deployment batch size (e.g. before a run); results are bit-identical with or without it."""
+        self._need_handle("autotune")
+        self._check_lengths(lens_host)
+        B, lmax = int(lens_host.shape[0]), int(lens_host.max())
+        if B > self.max_batch(lmax):
+            raise ValueError("autotune: batch exceeds one library call (Model.max_batch)")
+        lens_host = np.ascontiguousarray(lens_host, dtype=np.int32)
+        L = nv.lib()
+        ws = self._ws.get(L.rs_workspace_bytes(self._h, B, lmax))
+        probs, _ = _outputs(self.device, (B, 2))
+        changed = C.c_int32(0)
+        nv.check(L.rs_autotune(self._h, sig_dev.data_ptr(), off_dev.data_ptr(), len_dev.data_ptr(), lens_host.ctypes.data, B,
+                               int(lens_host.min()), lmax, ws.data_ptr(), ws.numel(), probs.data_ptr(), C.byref(changed), _stream_ptr(self.device)),
+                 "rs_autotune")
+        return changed.value
 
 
 _CONCURRENT_BELOW_SAMPLES = 1800 * 4096          # csrc/api.hip, rs_classify_ensemble: kConcurrentBelowSamples
@@ -731,29 +739,25 @@ def classify_raw_ensemble(models, sig_dev: torch.Tensor, off_dev: torch.Tensor, 
     m0._check_lengths(lens_host)
     B, lmax = int(lens_host.shape[0]), int(lens_host.max())
     lens_host = np.ascontiguousarray(lens_host, dtype=np.int32)
+    probs, _ = _outputs(m0.device, (len(models), B, 2), out)
     if any(m._h is None for m in models):
         # a generic conv program (depth > 1 / kernels other than 3) among the models: one classify_raw per model and
         # the decision kernel on their probabilities - the same arithmetic, just not one library call
-        probs = out if out is not None else torch.empty((len(models), B, 2), dtype=torch.float32, device=m0.device)
         for k, m in enumerate(models):
             m.classify_raw(sig_dev, off_dev, len_dev, lens_host, out=probs[k])
         if decision is not None:
             nv.check(nv.lib().rs_decide(probs.data_ptr(), len(models), B, len_dev.data_ptr(), int(max_len), float(threshold),
                                         int(mode), decision.data_ptr(), _stream_ptr(m0.device)), "rs_decide")
         return probs
-    mb = min(m.call_batch(B, lmax) for m in models)
-    if B > mb:                                                         # split: reads are independent
-        probs = out if out is not None else torch.empty((len(models), B, 2), dtype=torch.float32, device=m0.device)
-        for s0 in range(0, B, mb):
-            s1 = min(B, s0 + mb)
-            part = classify_raw_ensemble(models, sig_dev, off_dev[s0:s1].contiguous(), len_dev[s0:s1].contiguous(),
-                                         lens_host[s0:s1], decision=None if decision is None else decision[s0:s1],
-                                         max_len=max_len, threshold=threshold, mode=mode)
-            probs[:, s0:s1] = part
+    parts = _call_bounds(B, min(m.call_batch(B, lmax) for m in models))
+    if parts:
+        for s0, s1 in parts:
+            probs[:, s0:s1] = classify_raw_ensemble(models, sig_dev, off_dev[s0:s1].contiguous(), len_dev[s0:s1].contiguous(),
+                                                    lens_host[s0:s1], decision=None if decision is None else decision[s0:s1],
+                                                    max_len=max_len, threshold=threshold, mode=mode)
         return probs
     L = nv.lib()
     ws = m0._ws.get(_ensemble_bytes(models, B, lmax))
-    probs = out if out is not None else torch.empty((len(models), B, 2), dtype=torch.float32, device=m0.device)
     hs = (C.c_void_p * len(models))(*[m._h for m in models])
     nv.check(L.rs_classify_ensemble(hs, len(models), sig_dev.data_ptr(), off_dev.data_ptr(), len_dev.data_ptr(),
                                     lens_host.ctypes.data, B, int(lens_host.min()), lmax, ws.data_ptr(), ws.numel(), probs.data_ptr(),

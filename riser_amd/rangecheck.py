@@ -14,10 +14,8 @@ Without real signals at hand it uses the synthetic raw reads of riser_amd.synth 
 import argparse
 import sys
 
-import numpy as np
 import torch
 
-from . import _native as nv
 from . import synth
 from .model import Model
 from .preprocess import pack_reads
@@ -32,19 +30,15 @@ def activation_range(state, config=None, signals=None, device=None) -> list:
     if signals is None:
         signals = [synth.make_raw_read(4242, rid, 12000 + 37 * rid, polya=bool(rid % 5))[2048:] for rid in range(64)]
     m = Model(state, config, None, "range", dtype="f32w", device=dev)
-    lens = [len(s) for s in signals]
     sig, off, ln, lh = pack_reads(list(signals), dev)
-    info = m.layer_info()
     out = []
     try:
         for i in range(1, m.n_layers):
-            U, bases = m.block_samples(i), m.block_bases(lens, i)
-            cap = torch.zeros((int(bases[-1]) * (U >> (i + 1)), info[i]["cp_out"]), dtype=torch.float32, device=dev)
-            nv.check(nv.lib().rs_debug_capture_layer(m._h, i, cap.data_ptr(), cap.numel() * 4), "rs_debug_capture_layer")
-            m.classify_raw(sig, off, ln, lh)
+            cap = torch.zeros(m.layer_rows(lh, i)[:2], dtype=torch.float32, device=dev)
+            with m.capture_layer(i, cap):
+                m.classify_raw(sig, off, ln, lh)
             out.append(float(cap.abs().max().item()))
     finally:
-        nv.lib().rs_debug_capture_layer(m._h, -1, None, 0)
         m.close()
     return out
 

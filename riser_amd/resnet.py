@@ -9,12 +9,13 @@ conv / max-pool program (csrc/seqnet.hip) - parity-grade kernels, not the tuned 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
 
 from . import _native as nv
-from ._family import FamilyNet
+from ._family import FamilyNet, load_state
 
 _BN_EPS = 1e-5
 
@@ -199,6 +200,18 @@ class SeqNet(FamilyNet):
             out.append(d)
         return out
 
+    @functools.cached_property
+    def min_length(self) -> int:
+        """shortest input the program accepts (torch raises below it: kernel larger than the padded input, empty pooling)"""
+        lo, hi = 1, 1 << 16
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if self._fn("workspace_bytes")(self._h, 1, mid):
+                hi = mid
+            else:
+                lo = mid + 1
+        return lo
+
     @property
     def ragged_ok(self) -> bool:
         """True when forward_ragged can run this program (all of its ops inside fused launches: a ResNet's stem and blocks)"""
@@ -236,8 +249,7 @@ class ResNetModel:
         """dtype "bf16x3": the stem and the residual blocks in split precision on the bf16 MFMA (SeqNet)."""
         self.target, self.logger = target, logger
         c = config.resnet
-        sd = state if isinstance(state, dict) else torch.load(state, map_location="cpu")
-        sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
+        sd = load_state(state)
         if int(c.n_classes) != 2:
             raise ValueError("riser_amd supports two-class heads only")
         self._net = SeqNet(*build_program(sd, c), device=device, dtype=dtype)

@@ -13,10 +13,9 @@ from __future__ import annotations
 import ctypes as C
 
 import numpy as np
-import torch
 
 from . import _native as nv
-from ._family import FamilyNet
+from ._family import FamilyNet, load_state
 
 
 def _fold_weight_norm(sd, prefix):
@@ -47,7 +46,7 @@ def build_tcn_program(sd, c, bottleneck: bool):
     """(blocks, fc_w, fc_b) of a reference TCN (bottleneck=False, riser/nets/tcn.py) or TCNBot (riser/nets/tcn_bot.py)
     state dict.  blocks[i] = dict(convs=[dict(w [co, ci, k] fp32, b, k, causal)], shortcut=(w [co, ci], b) or None,
     base=d_{i+1} / d_i, dilation=d_i).  Every conv is followed by a ReLU; the block output is relu(convs + residual)."""
-    sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
+    sd = load_state(sd)
     k = int(c.kernel)
     n_layers = int(c.n_layers)
     n_filters = int(c.n_filters)
@@ -141,6 +140,7 @@ class TCNNet(FamilyNet):
     csrc/tcn_x3.hip: rs_tcn_set_mode)"""
 
     _PREFIX = "rs_tcn"
+    min_length = 1                  # causal convs: any read of one sample or more has a last position
     _MODES = {"f32": ("f32", nv.RS_F32), "f32w": ("f32", nv.RS_F32W), "fp32": ("f32", nv.RS_F32),
               "bf16x3": ("bf16x3", nv.RS_BF16X3)}
 

@@ -18,6 +18,7 @@ Batches of 576 and 640 full-length reads run F(4,3) and F(2,3) layers as head + 
 and RS_NO_RECT_ORDER=1.
 The tolerances are about four times the largest gap measured on an MI355X (below, next to each other); on the CPU every mutant
 of convnet_ref (a defect of the float64 reference) must miss by more than ten times the tolerance, so the bars can see them."""
+import contextlib
 import re
 import time
 
@@ -168,20 +169,13 @@ def _batch(n_layers, dev):
 def _forward(m, dev, layer=None):
     """(probs, logits) of the ragged batch, and the output buffer of conv layer `layer` as the device laid it out"""
     import torch
-    from riser_amd import _native as nv
     x, lens = _batch(m.n_layers, dev)
     cap = None
     if layer is not None:
-        info = m.layer_info()[layer]
-        rows = int(m.block_bases(lens, layer)[-1]) * (info["block_samples"] >> (layer + 1))
-        cap = torch.full((rows, info["cp_out"]), float("nan"), dtype=torch.float32, device=dev)
-        nv.check(nv.lib().rs_debug_capture_layer(m._h, layer, cap.data_ptr(), cap.numel() * 4), "capture")
-    try:
+        cap = torch.full(m.layer_rows(lens, layer)[:2], float("nan"), dtype=torch.float32, device=dev)
+    with m.capture_layer(layer, cap) if layer is not None else contextlib.nullcontext():
         probs, logits = m.forward_batch(x, lens, return_logits=True)
         torch.cuda.synchronize(dev)
-    finally:
-        if layer is not None:
-            nv.check(nv.lib().rs_debug_capture_layer(m._h, -1, None, 0), "capture off")
     return probs, logits, cap
 
 

@@ -18,6 +18,7 @@ its own signal, NaNs behind every read):
 The bars are about four times the largest gap measured on an MI355X (below, next to each other;
 profiles/h16_layers_gpu_tests.txt); on the CPU every mutant of h16_ref (a defect of the float64 layer) must miss by more than
 ten times the bar of the layer class it hits."""
+import contextlib
 import re
 import time
 
@@ -427,24 +428,17 @@ def _forward(m, dev, capfd, layer=None, raw_reads=False):
     """(probs, logits, bytes of conv layer `layer`'s output buffer as the device laid it out, layers whose launch took the
     thin kernel) of the ragged batch through forward_batch, or through classify_raw on the int16 reads"""
     import torch
-    from riser_amd import _native as nv
     x, packed, lens = _batch(m.n_layers, dev)
     cap = None
     if layer is not None:
-        info = m.layer_info()[layer]
-        rows = int(m.block_bases(lens, layer)[-1]) * (info["block_samples"] >> (layer + 1))
-        cap = torch.full((H.capture_bytes(rows, info["cp_out"], info["rows_format"]),), 0xA5, dtype=torch.uint8, device=dev)
-        nv.check(nv.lib().rs_debug_capture_layer(m._h, layer, cap.data_ptr(), cap.numel()), "capture")
+        cap = torch.full((H.capture_bytes(*m.layer_rows(lens, layer)),), 0xA5, dtype=torch.uint8, device=dev)
     capfd.readouterr()
-    try:
+    with m.capture_layer(layer, cap) if layer is not None else contextlib.nullcontext():
         if raw_reads:
             probs, logits = m.classify_raw(*packed, return_logits=True)
         else:
             probs, logits = m.forward_batch(x, lens, return_logits=True)
         torch.cuda.synchronize(dev)
-    finally:
-        if layer is not None:
-            nv.check(nv.lib().rs_debug_capture_layer(m._h, -1, None, 0), "capture off")
     err = capfd.readouterr().err
     thin = {int(i) for i, what in re.findall(r"\[thin-or-ring\] layer (\d+):[^\n]*-> (thin|ring)", err) if what == "thin"}
     return probs.cpu().numpy(), logits.cpu().numpy(), None if cap is None else cap.cpu().numpy(), thin

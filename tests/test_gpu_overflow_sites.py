@@ -28,6 +28,7 @@ captures come from the same model in the two-launch form, which test_h16_streami
 the flag is then read behind a call without capture, which runs the one launch.
 
 Every case prints an OVERFLOW_SITE line per window (pytest -s): site, mode, net, kernel tile, amplitude or scale, first inf."""
+import contextlib
 import math
 
 import numpy as np
@@ -261,27 +262,22 @@ class Rig:
     def run(self, m, batch, layer=None):
         """one call of the entry point under test -> (decoded hi halves of `layer`'s output or None, saturated())"""
         import torch
-        from riser_amd import _native as nv
         lens = batch[2] if batch[0] == "forward" else batch[4]
         cap = None
         if layer is not None:
-            info = m.layer_info()[layer]
-            rows = int(m.block_bases(lens, layer)[-1]) * (info["block_samples"] >> (layer + 1))
-            cap = torch.zeros(rows * info["cp_out"], dtype=torch.int16, device=self.dev)
-            nv.check(nv.lib().rs_debug_capture_layer(m._h, layer, cap.data_ptr(), cap.numel() * 2), "rs_debug_capture_layer")
-        try:
+            rows, cp, fmt = m.layer_rows(lens, layer)
+            cap = torch.zeros(rows * cp, dtype=torch.int16, device=self.dev)
+        with m.capture_layer(layer, cap) if layer is not None else contextlib.nullcontext():
             if batch[0] == "forward":
                 probs = m.forward_batch(batch[1], lens)
             else:
                 probs = m.classify_raw(batch[1], batch[2], batch[3], lens)
-        finally:
-            nv.lib().rs_debug_capture_layer(m._h, -1, None, 0)
         assert tuple(probs.shape) == (len(lens), 2)
         sat = m.saturated()
         assert not m.saturated()                                        # cleared by the read
         if cap is None:
             return None, sat
-        return R.decode_hi(cap.cpu().numpy(), info["rows_format"], info["cp_out"], info["c_out"]), sat
+        return R.decode_hi(cap.cpu().numpy(), fmt, cp, m.channels[layer]), sat
 
     def layer0_oracle(self, m_key, lens, base, read, s0, s1, amplitude):
         """layer 0's output in fp32 (oracle.riser_oracle.conv_block) on the rows of a float batch, per read [C, L // 2]"""

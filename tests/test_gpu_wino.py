@@ -140,7 +140,6 @@ def test_layerwise_activations_vs_oracle(dev, dtype):
     """every conv block's output buffer (rs_debug_capture_layer) against the oracle's activations: valid rows
     within fp32 round-off, every padding row of every read's slot exactly zero (the next layer's 'same'
     padding depends on it)."""
-    from riser_amd import _native as nv
     from riser_amd.preprocess import pack_reads
     m = get_model(2, dev, dtype)
     sd = synth.make_state_dict(2)
@@ -159,10 +158,10 @@ def test_layerwise_activations_vs_oracle(dev, dtype):
     for i in range(1, m.n_layers):
         U, bases = m.block_samples(i), m.block_bases(lens, i)
         assert list(np.diff(bases)) == [n // U + 1 for n in lens]
-        P_out, cp = U >> (i + 1), info[i]["cp_out"]
-        cap = torch.full((int(bases[-1]) * P_out, cp), float("nan"), dtype=torch.float32, device=dev)
-        nv.check(nv.lib().rs_debug_capture_layer(m._h, i, cap.data_ptr(), cap.numel() * 4), "capture")
-        m.classify_raw(sig, off, ln, lh)
+        P_out = U >> (i + 1)
+        cap = torch.full(m.layer_rows(lens, i)[:2], float("nan"), dtype=torch.float32, device=dev)
+        with m.capture_layer(i, cap):
+            m.classify_raw(sig, off, ln, lh)
         got_all = cap.cpu().numpy()
         for b, n in enumerate(lens):
             got = got_all[bases[b] * P_out: bases[b + 1] * P_out]
@@ -173,7 +172,6 @@ def test_layerwise_activations_vs_oracle(dev, dtype):
             assert np.abs(got[:L_out, :C] - ref).max() < 2e-4 * scale, (i, b)
             assert not got[L_out:, :].any(), (i, b)                 # padding rows of the read's blocks
             assert not got[:, C:].any(), (i, b)                     # padding channels
-    nv.check(nv.lib().rs_debug_capture_layer(m._h, -1, None, 0), "capture off")
 
 
 def test_winograd_f43_layers(dev, monkeypatch):
@@ -181,7 +179,6 @@ def test_winograd_f43_layers(dev, monkeypatch):
     is created): probabilities within the fp32 bar of the oracle and of the all-F(2,3) model, labels identical,
     on a full-length batch, a mixed-length batch and a single read; activations of an F(4,3) layer within
     round-off of the oracle."""
-    from riser_amd import _native as nv
     from riser_amd.model import Model
     from riser_amd.preprocess import pack_reads
     sd = synth.make_state_dict(1)
@@ -207,10 +204,10 @@ def test_winograd_f43_layers(dev, monkeypatch):
     assert m.block_samples() == 8192                              # F(4,3) on the last layer doubles the (coarse) block
     U, bases = m.block_samples(i), m.block_bases(lens, i)
     assert U == 1024                                              # ... the early layers keep their fine blocks
-    P_out, cp = U >> (i + 1), m.layer_info()[i]["cp_out"]
-    cap = torch.full((int(bases[-1]) * P_out, cp), float("nan"), dtype=torch.float32, device=dev)
-    nv.check(nv.lib().rs_debug_capture_layer(m._h, i, cap.data_ptr(), cap.numel() * 4), "capture")
-    m.classify_raw(sig, off, ln, lh)
+    P_out = U >> (i + 1)
+    cap = torch.full(m.layer_rows(lens, i)[:2], float("nan"), dtype=torch.float32, device=dev)
+    with m.capture_layer(i, cap):
+        m.classify_raw(sig, off, ln, lh)
     got_all = cap.cpu().numpy()
     for b, s in enumerate(sigs):
         got = got_all[bases[b] * P_out: bases[b + 1] * P_out]

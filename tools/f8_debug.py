@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from riser_amd import _native as nv, synth
+from riser_amd import synth
 from riser_amd.model import Model
 from riser_amd.preprocess import pack_reads
 from tests import h16_ref as H
@@ -25,13 +25,10 @@ n_layers = models["f16x3"].n_layers
 for i in range(3, n_layers):
     out = {}
     for dt, m in models.items():
-        U, bases = m.block_samples(i), m.block_bases([L] * B, i)
-        P_out, cp = U >> (i + 1), info[dt][i]["cp_out"]
-        rows = int(bases[-1]) * P_out
+        rows, cp, _ = m.layer_rows(lens, i)
         cap = torch.zeros(rows * cp * 2 + 256 + (cp // 64) * (rows + 4) * 4 + 1024, dtype=torch.uint8, device=dev)
-        nv.check(nv.lib().rs_debug_capture_layer(m._h, i, cap.data_ptr(), cap.numel()), "capture")
-        p = m.classify_raw(sig, off, ln, lens).cpu().numpy()
-        nv.check(nv.lib().rs_debug_capture_layer(m._h, -1, None, 0), "capture off")
+        with m.capture_layer(i, cap):
+            p = m.classify_raw(sig, off, ln, lens).cpu().numpy()
         out[dt] = (cap.cpu().numpy(), rows, cp, p)
     C = info["f16x3"][i]["c_out"]
     raw, rows, cp, p3 = out["f16x3"]
