@@ -238,10 +238,11 @@ using KernelFn = void (*)(const StreamF32Args);
 }  // namespace
 
 // layers 0 + 1 qualify when layer 1 is the shipped shape class: 20 padded input channels in one chunk,
-// at most 32 outputs, and an output slot of at least 16 rows
+// at most 32 outputs, and an output slot of at least 16 rows - and packed for F(2,3): RS_WINO4 can put F(4,3) on layer 1,
+// whose [6][20] component rows this kernel would read as [4][20]
 bool conv_stream_f32_ok(const ConvLayerDev& L1, int c0, int P_in1) {
-    return L1.cp_in == 20 && c0 <= 20 && L1.plan.kc == 20 && L1.plan.nch == 1 && L1.c_out <= 32 && P_in1 >= 64 &&
-           !L1.hooks->no_stream_f32;
+    return L1.wino_m == 2 && L1.cp_in == 20 && c0 <= 20 && L1.plan.kc == 20 && L1.plan.nch == 1 && L1.c_out <= 32 &&
+           P_in1 >= 64 && !L1.hooks->no_stream_f32;
 }
 
 int launch_conv_stream_f32(const ConvLayerDev& L1, const float* d_xs, const float* d_w0, int c0, float* d_y,

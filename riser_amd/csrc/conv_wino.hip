@@ -158,10 +158,11 @@ bool conv_wino_shape_ok(const ConvLayerDev& L, int k) {
 }
 
 // layer 0 can be folded into this layer's staging when the layer is the shipped net's layer 1
-// (20 input channels = one 20-channel chunk, <= 32 outputs) and a tile spans at most two reads
+// (20 input channels = one 20-channel chunk, <= 32 outputs) and a tile spans at most two reads; an F(4,3) layer 1 (RS_WINO4)
+// runs conv_wino4.hip, which has no such staging: layer 0 must then be a launch of its own
 bool conv_wino_can_fuse0(const ConvLayerDev& L, int P_in) {
-    return L.cp_in == 20 && L.plan.kc == 20 && L.plan.nch == 1 && L.c_out <= kFusedBN && P_in >= 2 * kFusedBMP + 2 &&
-           !L.hooks->no_fuse0;
+    return L.wino_m == 2 && L.cp_in == 20 && L.plan.kc == 20 && L.plan.nch == 1 && L.c_out <= kFusedBN &&
+           P_in >= 2 * kFusedBMP + 2 && !L.hooks->no_fuse0;
 }
 
 int launch_conv_wino(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len, int B, int P_in,

@@ -1,6 +1,7 @@
-"""Helpers of tests/test_gpu_f32_shapes.py: the fp32 conv kernels' tile-shape tables read out of the sources, a mirror of their
-LDS footprints, the sweep's nets and read lengths, and a float64 reference of ONE ConvNet layer (direct and as Winograd
-F(4,3)) with deliberate defects (MUTANTS) that the sweep's tolerances must be able to see.  numpy only."""
+"""Helpers of tests/test_gpu_f32_shapes.py and tests/test_gpu_f32_thin.py: the fp32 conv kernels' tile-shape tables and the
+small-batch kernel's instantiations read out of the sources, a mirror of their LDS footprints, the sweep's nets and read
+lengths (normalised rows and raw int16), and a float64 reference of ONE ConvNet layer (direct and as Winograd F(4,3)) with
+deliberate defects (MUTANTS) that the sweep's tolerances must be able to see.  numpy only."""
 import os
 import re
 
@@ -93,6 +94,43 @@ VARIANTS = {
     "narrow_w4_kc16": (NARROW, "f32w", {"RS_WINO4": _W4_ALL(6), "RS_PLAN_KC": _KC_ALL(6, 16)}, True),
     "narrow_w4_kc20": (NARROW, "f32w", {"RS_WINO4": _W4_ALL(6), "RS_PLAN_KC": _KC_ALL(6, 20)}, True),
 }
+# The nets of tests/test_gpu_f32_thin.py (the fp32 streaming kernel K3s, conv_stream_f32.hip, and the small-batch kernel K3m,
+# conv_small_f32.hip): the Winograd variants above, and 6-layer nets with NARROW's tail whose first two layers sit on the
+# streaming kernel's edges.  conv_stream_f32_ok wants layer 1 as F(2,3) with cp_in == 20 (row_pitch: c0 rounded up to 4, so
+# c0 = 17 .. 20), kc == 20 and nch == 1 (plan_static_wino at 20 padded channels: one chunk of 20 costs 21.5, two of 16 cost 35,
+# one of 24 costs 25.5) and c1 <= 32; the F(4,3) forms leave layer 1 to F(2,3) and put layers 2-5 behind the streaming kernel.
+_TAIL = NARROW[2:]
+_W4_TAIL = ",".join(str(i) for i in range(2, 6))
+THIN_VARIANTS = {v: VARIANTS[v] for v in ("ship_f32w", "ship_w2", "ship_w4_kc16", "ship_w4_kc20", "narrow_w2", "narrow_w4_kc16",
+                                          "narrow_w4_kc20")}
+THIN_VARIANTS.update({
+    "stream_18_13": ((18, 13) + _TAIL, "f32w", {}, False),        # layer-0 lanes above the real channels; NT = 1, c_out < 16
+    "stream_19_29": ((19, 29) + _TAIL, "f32w", {}, False),        # NT = 2 with a partial second sub-tile
+    "stream_17_32": ((17, 32) + _TAIL, "f32w", {}, False),        # NT = 2, both sub-tiles whole
+    "stream_18_13_w4_kc20": ((18, 13) + _TAIL, "f32w", {"RS_WINO4": _W4_TAIL, "RS_PLAN_KC": _KC_ALL(6, 20)}, False),
+    "stream_19_29_w4_kc16": ((19, 29) + _TAIL, "f32w", {"RS_WINO4": _W4_TAIL, "RS_PLAN_KC": _KC_ALL(6, 16)}, False),
+})
+# the variants whose layer 1 the streaming kernel takes on the raw entry point (an F(4,3) layer 1 is not its packing; the
+# narrow net's layer 1 has 8 padded input channels)
+THIN_STREAMING = ("ship_f32w", "ship_w2") + tuple(v for v in THIN_VARIANTS if v.startswith("stream_"))
+
+
+def parse_small_instantiations():
+    """{(nc, kc, shared, nw)} of the conv_small_f32_kernel<...> instantiations that pick() of conv_small_f32.hip can return
+    (template arguments left out take the kernel template's defaults)"""
+    with open(os.path.join(CSRC, "conv_small_f32.hip")) as f:
+        text = f.read()
+    d = re.search(r"template\s*<int NC, int KC, bool SH = (true|false), int NW = (\d+)>\s*__global__", text)
+    m = re.search(r"KernelFn pick\([^)]*\)\s*\{(.*?)\n\}", text, re.S)
+    assert d and m
+    body = re.sub(r"//[^\n]*", "", m.group(1))
+    found = re.findall(r"conv_small_f32_kernel<\s*(\d+)\s*,\s*(\d+)\s*(?:,\s*(true|false)\s*(?:,\s*(\d+)\s*)?)?>", body)
+    assert len(found) == len(re.findall(r"conv_small_f32_kernel\s*<", body))       # every instantiation was understood
+    out = [(int(nc), int(kc), (sh or d.group(1)) == "true", int(nw or d.group(2))) for nc, kc, sh, nw in found]
+    assert len(set(out)) == len(out)
+    return set(out)
+
+
 _SD = {}
 
 
@@ -145,6 +183,27 @@ def reads(n_layers):
             s = synth.make_signals(20260104, 1, MAX_LEN, first_read=9100 + k)[0]
             _SIGNALS.append(ro.mad_normalise(s).astype(np.float32))
     return [_SIGNALS[k][MAX_LEN - n:] for k, n in enumerate(sweep_lengths(n_layers))]
+
+
+_RAW = []
+_RAW_NORM = {}
+
+
+def raw_reads(n_layers):
+    """the same 77 reads as raw int16 (the streaming kernel runs on the raw entry point only): read k is the last n_k samples of a
+    synthetic read of 16000 samples.  Packed (preprocess.pack_reads) they lie back to back: the sample in front of a read is
+    the last one of the read before it"""
+    if not _RAW:
+        for k in range(N_READS):
+            _RAW.append(synth.make_signals(20260104, 1, MAX_LEN, first_read=9100 + k)[0])
+    return [_RAW[k][MAX_LEN - n:] for k, n in enumerate(sweep_lengths(n_layers))]
+
+
+def raw_normalised(n_layers):
+    """what layer 0 reads of raw_reads: each read normalised on its own (the oracle's float64 rule), as fp32"""
+    if n_layers not in _RAW_NORM:
+        _RAW_NORM[n_layers] = [ro.mad_normalise(s).astype(np.float32) for s in raw_reads(n_layers)]
+    return _RAW_NORM[n_layers]
 
 
 # ------------------------------------------------------------------------------------------------ one layer in float64
@@ -207,6 +266,38 @@ def layer_f64(x, w, b, mutant=None, kc=16, prev_last=None, wino4=False):
     if mutant == "last_pair_not_pooled" and Lo:
         out[:, Lo - 1] = y[:, 2 * Lo - 2]
     return out
+
+
+def layer_f64_reads(xs, w, b):
+    """layer_f64 (no mutant) of several reads at once: xs [k] = [C_in, L_k] -> [k] = [C_out, L_k // 2].  The reads lie side by
+    side with their zero columns between them, so every tap is ONE product and the weights are converted and read once
+    (per read, the late layers of the shipped net spend their time there).  Equal to layer_f64 up to float64 round-off."""
+    w = np.asarray(w, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    Ls = [int(x.shape[1]) for x in xs]
+    starts = np.concatenate([[0], np.cumsum([L + 2 for L in Ls])]).astype(np.int64)
+    xp = np.zeros((w.shape[1], int(starts[-1])))
+    for s, x in zip(starts, xs):
+        xp[:, s + 1:s + 1 + x.shape[1]] = x
+    T = xp.shape[1] - 2
+    y = w[:, :, 0] @ xp[:, 0:T] + w[:, :, 1] @ xp[:, 1:T + 1] + w[:, :, 2] @ xp[:, 2:T + 2]
+    y = np.maximum(y + b[:, None], 0)
+    out = []
+    for s, L in zip(starts, Ls):                                    # column s + p of y: position p of the read
+        Lo = L // 2
+        out.append(np.maximum(y[:, s:s + 2 * Lo:2], y[:, s + 1:s + 2 * Lo:2]))
+    return out
+
+
+def forward_f64_reads(sd, xs):
+    """float64 logits [k, 2] of the reads xs [k] = [L_k] through the whole net (the `gap_fc` head: mean over the positions,
+    then the Linear layer), layer by layer with layer_f64_reads"""
+    n_layers = sum(1 for k in sd if k.startswith("layers.") and k.endswith(".0.weight"))
+    hs = [np.asarray(x, dtype=np.float64)[None, :] for x in xs]
+    for i in range(n_layers):
+        hs = layer_f64_reads(hs, sd[f"layers.{i}.0.weight"], sd[f"layers.{i}.0.bias"])
+    feat = np.stack([h.mean(axis=1) for h in hs])
+    return feat @ np.asarray(sd["classifier.2.weight"], dtype=np.float64).T + np.asarray(sd["classifier.2.bias"], dtype=np.float64)
 
 
 def layer_inputs(sd, x, upto):
