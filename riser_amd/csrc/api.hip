@@ -64,6 +64,7 @@ Hooks Hooks::from_env() {
     text("RS_EMU_ROWS", h.emu_rows, sizeof(h.emu_rows));
     if (const char* e = getenv("RS_SMALL_F32_WAVES")) h.small_f32_waves = atoi(e);
     if (const char* e = getenv("RS_H16_WRES")) h.h16_wres = atoi(e) != 0;
+    if (const char* e = getenv("RS_WRES_F32")) h.wres_f32 = atoi(e) != 0;
     if (const char* e = getenv("RS_THIN_H16_ROWS")) h.thin_h16_rows = atoi(e);
     if (const char* e = getenv("RS_F8_MIN_CIN")) h.f8_min_cin = atoi(e);
     if (const char* e = getenv("RS_X3_TAIL")) h.x3_tail = atoi(e) != 0;

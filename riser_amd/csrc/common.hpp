@@ -84,6 +84,8 @@ struct Hooks {
     bool x3_tail = true;             // RS_X3_TAIL=0: split-precision layers whose last panel holds <= 8 channels keep it as three 32-wide K steps instead of ONE merged step (conv_ring_h16.hip: TAIL)
     int f8_min_cin = 200;            // RS_F8_MIN_CIN: RS_F16XF8 puts a layer on the 8-bit kernel from this many input channels on (convnet_pack.hpp: f8_eligible)
     bool h16_wres = true;            // RS_H16_WRES=0: narrow 16-bit layers on the ring kernel instead of the weights-resident one
+    int wres_f32 = -1;               // RS_WRES_F32: 0 = never the fp32 weights-resident kernel (conv_wres_f32.hip), 1 = on every eligible layer
+                                     // whatever the launch size (tests, A/B; default -1: on launches that give every wave a run of steps)
     char plan_kc[128] = "";          // RS_PLAN_KC "layer:kc;...": forces the channel chunk of an F(4,3) layer (convnet_model.hpp: plan_static_wino4)
     char x3_terms[128] = "";         // RS_X3_TERMS "layer:mask;...": -DRS_X3_MASK measurement builds only (ConvLayerDev::x3_terms)
     bool wino4_set = false;          // RS_WINO4: comma list of the layers that run F(4,3) ("none": F(2,3) everywhere), instead of
@@ -218,6 +220,12 @@ double conv_wino_plan_cost(int64_t rows_out, int n16, int kc, int nch, int num_c
 double conv_wino_launch_cost(int64_t rows_out, int n16, int kc, int nch, int num_cu, bool* thin_out);
 int launch_conv_small_f32(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len, int B, int P_in,
                           int layer_index, int num_cu, hipStream_t st, int* bm_out, int* bn_out);
+// fp32 Winograd, narrow layers with chunks of 16: the layer's whole weight tensor resident in LDS, a run of 16-unit steps per
+// wave, no barrier behind the prologue (conv_wres_f32.hip); bit-identical to conv_wino.hip / conv_wino4.hip
+bool conv_wres_f32_ok(const ConvLayerDev& L);
+bool conv_wres_f32_fills(const ConvLayerDev& L, int64_t rows_in, int num_cu);   // the launch gives every wave slot a run of several steps
+int launch_conv_wres_f32(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len, int B, int P_in,
+                         int layer_index, int num_cu, hipStream_t st, int* bm_out, int* bn_out);
 // narrow 16-bit layers (C_in <= 32, C_out <= 48): per-wave streaming kernel, optionally with ConvNet
 // layer 0 folded in (fuse_xs = normalised signals at the padded pitch behind 16 zero bytes)
 bool conv_stream_h16_ok(const ConvLayerDev& L, int P_in);

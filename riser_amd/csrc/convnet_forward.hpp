@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "convnet_model.hpp"
 #include "convnet_workspace.hpp"
+#include "tile_plan.hpp"
 
 namespace rs {
 namespace {
@@ -38,6 +39,7 @@ void prof_mark(rs_model* m, int stage, hipStream_t st) {
 enum class Kernel {
     StreamF32,      // fp32 Winograd: layers 0 + 1 as one LDS-free streaming launch (conv_stream_f32.hip)
     SmallF32,       // fp32 Winograd on a launch of a few rows: a wave per 16 x 16 tile (conv_small_f32.hip)
+    WresF32,        // fp32 Winograd, narrow layers of a full launch: weights resident in LDS, a run of steps per wave (conv_wres_f32.hip)
     Wino4,          // F(4,3) (conv_wino4.hip)
     Wino2,          // F(2,3) (conv_wino.hip), optionally with layer 0 folded into layer 1's staging
     DirectF32,      // RS_F32 (conv_f32.hip)
@@ -86,7 +88,7 @@ Fuse0 fuse0_of(const rs_model* m, bool packed_x, int U0) {
 }
 
 // The kernel of layer i >= 1 on a launch of NB blocks of P_in input rows.  The order of the questions is the precedence:
-//   RS_F32W:  streaming 0 + 1  >  small-batch  >  F(4,3) / F(2,3) by the layer's packing
+//   RS_F32W:  streaming 0 + 1  >  weights-resident (full launches of narrow layers)  >  small-batch  >  F(4,3) / F(2,3) by the layer's packing
 //   RS_F32:   direct
 //   16-bit:   streaming 0 + 1 + 2  >  streaming  >  F8 rows  >  thin (split precision)  >  weights-resident  >  ring
 // (rs_autotune runs no small-batch and no thin launch: it times the tiled kernels' shapes)
@@ -97,6 +99,16 @@ Kernel select_kernel(const rs_model* m, int i, int NB, int P_in, const Fuse0& fu
     if (m->dtype == RS_F32W) {
         if (i == 1 && fuse0.stream_f32) return Kernel::StreamF32;
         const Kernel tiled = L.wino_m == 4 ? Kernel::Wino4 : Kernel::Wino2;
+        // narrow layers whose whole weight tensor fits LDS next to a private activation image per wave (layers 2 and 3 of the
+        // shipped net), on launches that give every wave slot a run of steps (RS_WRES_F32=1: whatever the launch size).  It
+        // steps aside for everything that asks for the tiled or the small kernel by name: a forced small kernel, rs_autotune,
+        // RS_NO_STREAM_F32 ("tiled kernels on every layer"), a forced tile shape of this layer - and for layer 1 while
+        // layer 0 is folded into its staging
+        if (!(i == 1 && fuse0.wino) && m->hooks.small_f32_waves <= 0 && !m->tuning && !m->hooks.no_stream_f32 && conv_wres_f32_ok(L)) {
+            int wm, wn, mt, nt;
+            const bool pinned = next_layer_shape(L.wino_m == 4 ? m->hooks.force_wino4 : m->hooks.force_wino, i, &wm, &wn, &mt, &nt) != nullptr;
+            if (!pinned && (m->hooks.wres_f32 > 0 || conv_wres_f32_fills(L, rows_in, m->num_cu))) return Kernel::WresF32;
+        }
         // fp32 Winograd layers of a launch with only a handful of rows (Model.classify at batch 1, a thin ReadUntil batch):
         // one wave per 16 x 16 tile instead of 256-row tiles that are mostly padding (conv_small_f32.hip; same bits)
         // (not layer 1 when layer 0 is folded into its staging: nothing has written that layer's input)
@@ -258,6 +270,9 @@ int forward_impl(rs_model* m, const float* d_x, int64_t ldx, const int32_t* d_le
             case Kernel::SmallF32:
                 return launch_conv_small_f32(L, static_cast<const float*>(x), static_cast<float*>(y), d_blen, NB, P_in, i, m->num_cu,
                                              st, bm, bn);
+            case Kernel::WresF32:
+                return launch_conv_wres_f32(L, static_cast<const float*>(x), static_cast<float*>(y), d_blen, NB, P_in, i, m->num_cu, st,
+                                            bm, bn);
             case Kernel::Wino4:
                 return launch_conv_wino4(L, static_cast<const float*>(x), static_cast<float*>(y), d_blen, NB, P_in, i, m->num_cu,
                                          check_dead, st, bm, bn);
