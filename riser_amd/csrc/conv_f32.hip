@@ -26,7 +26,7 @@
 // latency, the epilogue's stores and the next tile's prologue all hide under MFMA issue.
 // LDS rows are KC+2 floats (= 2 mod 4): the 16 rows x 2 k-groups that a 32-lane half reads
 // with ds_read_b32 then fall in 32 distinct banks.
-#include "common.hpp"
+#include "conv_wino_device.hpp"
 #include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
@@ -39,8 +39,6 @@
 
 namespace rs {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Diagnostic build only (-DRS_ITEM_STAMPS): per-phase s_memtime sums of one item loop, written to
 // ConvArgs::stamps[2048 + ...]; never compiled into the shipped library.
@@ -226,14 +224,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_f32_kernel(const ConvArgs a
                 const int b = tm0 / P_in_;
                 const int t0 = tm0 - b * P_in_;
                 if (!(t0 + BM <= P_in_ && t0 >= (as_const_len(a.len)[b] >> (a.shift_out - 1)))) break;
-                // zero-fill the BM/2 x BN output tile (16-byte pieces; rows are cp_out wide)
-                const int pieces_per_row = BN / 4;
-                for (int f = threadIdx.x; f < (BM / 2) * pieces_per_row; f += blockDim.x) {
-                    const int rr = f / pieces_per_row, cc = (f - rr * pieces_per_row) * 4;
-                    const int prow = (tm0 >> 1) + rr, col = tn0 + cc;
-                    if (2 * prow < a.rows_in && col < a.cp_out)
-                        *reinterpret_cast<float4*>(a.y + (int64_t)prow * a.cp_out + col) = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
+                // the BM/2 x BN output tile; pooled row p exists while 2 p < rows_in
+                zero_fill_tile<BN, 2>(a.y, tm0 >> 1, BM / 2, tn0, a.rows_in, a.cp_out);
             }
             q = order_index();
         }

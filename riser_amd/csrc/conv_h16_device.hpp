@@ -1,35 +1,19 @@
 // Device-side primitives of the ConvNet's 16-bit conv kernels (conv_ring_h16.hip, conv_ring_f8.hip, conv_wres_h16.hip,
-// conv_thin_h16.hip, conv_stream_h16.hip): the vector types, the 16-bit MFMA, the 16-bit <-> fp32 conversions of plain and split
+// conv_thin_h16.hip, conv_stream_h16.hip): the 16-bit vector types (f32x4, u32x4, kOob and static_for are device_prelude.hpp's), the 16-bit MFMA, the 16-bit <-> fp32 conversions of plain and split
 // precision, the LDS-DMA piece, and the epilogue step the tiled kernels share.  Device-only, everything
 // force-inlined into an anonymous namespace: a kernel's code is what it was with the definitions in its own file.
 #pragma once
-#include "common.hpp"
-
-#include <utility>
+#include "device_prelude.hpp"
 
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// a buffer offset past every buffer (num_records < 2^31): loads return zeros, LDS-DMA writes zeros, stores are dropped
-constexpr unsigned kOob = 0x80000000u;
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
 
 template <bool F16>
 __device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f32x4& c) {

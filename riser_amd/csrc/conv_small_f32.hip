@@ -22,27 +22,13 @@
 // and every rounding in them) is that of the tiled kernels, so the results are BIT-IDENTICAL to theirs: a read classified
 // alone equals its row of a 512-read batch (tests/test_gpu_small.py).  The launch planner picks this kernel when the
 // launch has at most kSmallMaxWaves tiles (convnet_forward.hpp: select_kernel); layers 0 + 1 keep the streaming kernel.
-#include "common.hpp"
+#include "conv_wino_device.hpp"
 
 #include <algorithm>
 #include <utility>
 
 namespace rs {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
-constexpr unsigned kOob = 0x80000000u;
 
 struct SmallArgs {
     const float* x;        // [rows_in][cp_in]
@@ -79,13 +65,14 @@ struct SmallArgs {
 // component accumulators meet in LDS for the output transform.
 template <int NC, int KC, int NW = 1>
 struct SmallGeom {
-    static constexpr int R = NC == 4 ? 4 : 6;             // input rows of a unit
-    static constexpr int STRIDE = NC == 4 ? 2 : 4;        // input rows between consecutive units
-    static constexpr int KQ = KC / 4;                     // k-steps per chunk = 16-byte units per input row
+    using W = WinoGeom<NC - 2, KC>;                       // the tiled kernels' plane layout (conv_wino_device.hpp)
+    static constexpr int R = W::NC;                       // input rows of a unit
+    static constexpr int STRIDE = W::NP;                  // input rows between consecutive units = planes
+    static constexpr int KQ = W::KQ;                      // k-steps per chunk = 16-byte units per input row
     static constexpr int AR = 16 * STRIDE + (R - STRIDE); // input rows of the tile
-    static constexpr int S = KC + 2;                      // LDS pitch of a row (input and weight)
-    static constexpr int PLROWS = 17;                     // rows per plane: index (slab row / STRIDE) <= 16
-    static constexpr int A_LDS = STRIDE * PLROWS * S;     // floats
+    static constexpr int S = W::S;                        // LDS pitch of a row (input and weight)
+    static constexpr int PLROWS = W::PL16 / S;            // rows per plane: index (slab row / STRIDE) <= 16
+    static constexpr int A_LDS = W::IMG16;                // floats
     static constexpr int WR = 16 * NW;                    // weight rows of a wave: NW channel sub-tiles
     static constexpr int BUF = A_LDS + WR * S + 8;        // a wave's private image: input rows + weights + a dump slot for the lanes of a pass that hold no unit
     static constexpr int WBUF = WR * S + 8;               // ... weights only, when the input rows are shared
@@ -112,8 +99,7 @@ __device__ __forceinline__ void small_chain(const SmallArgs& a, float* lds, floa
     constexpr int A_PER = (A_UNITS + A_LANES - 1) / A_LANES, W_PER = (W_UNITS + 63) / 64;
     constexpr int ASH = A_LDS + 8;                 // one shared image (+ a dump slot)
     const int r = lane & 15, kq = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, a.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.x, a.x_bytes), rs_w = buffer_rsrc(a.w, a.w_bytes);
 
     // ---- staging maps: unit q = lane + 64 j.  Input rows before the buffer (row -1 of the first tile) and past its end
     // resolve to out-of-range offsets: zeros, the conv's 'same' padding at the batch edges (inside the batch the producer
@@ -302,8 +288,7 @@ __global__ __launch_bounds__(64 * NC) void conv_small_f32_kernel(const SmallArgs
     // ---- the components meet: [comp][lane] x 4 floats in LDS (the staging images are dead), one barrier, then wave h of
     // the first PR waves forms pooled row h of every unit: output transform, MaxPool, + bias, ReLU, length mask; 16 bytes
     // per lane ------------------------------------------------------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = buffer_rsrc(a.y, a.y_bytes), rs_b = buffer_rsrc(a.bias, a.bias_bytes);
     __syncthreads();                                                   // every wave is done with its staging image
     f32x4* meet = reinterpret_cast<f32x4*>(lds_all);
 #pragma unroll
@@ -328,23 +313,12 @@ __global__ __launch_bounds__(64 * NC) void conv_small_f32_kernel(const SmallArgs
         f32x4 o;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            float y0, y1;
-            if constexpr (NC == 4) {
-                const float m1 = m[0][q], m2 = m[1][q], m3 = m[2][q], m4 = m[3][q];
-                y0 = (m1 + m2) + m3;
-                y1 = (m2 - m3) - m4;
-            } else {
-                const float m0_ = m[0][q], m1 = m[1][q], m2 = m[2][q], m3 = m[3][q], m4 = m[4][q], m5 = m[5][q];
-                const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                if (h == 0) {
-                    y0 = (m0_ + s12) + s34;
-                    y1 = fmaf(2.0f, d34, d12);
-                } else {
-                    y0 = fmaf(4.0f, s34, s12);
-                    y1 = fmaf(8.0f, d34, d12) + m5;
-                }
-            }
-            o[q] = valid ? fmaxf(fmaxf(y0, y1) + bi[q], 0.0f) : 0.0f;
+            float mq[NC], p[PR];
+#pragma unroll
+            for (int k = 0; k < NC; ++k) mq[k] = m[k][q];
+            wino_output_pool<NC - 2>(p, mq);
+            const float ph = h == 0 ? p[0] : p[PR - 1];                // h < PR, wave-uniform
+            o[q] = valid ? fmaxf(ph + bi[q], 0.0f) : 0.0f;
         }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_y,
                                                in_range ? (unsigned)pr * (unsigned)(a.cp_out * 4) + coloff : kOob, 0, 0);

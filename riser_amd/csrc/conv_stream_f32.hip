@@ -20,7 +20,7 @@
 // Rows 2T+1, 2T+2 are also computed by the neighbouring lane (as its 2T'-1, 2T'): a 2x redundancy in
 // layer-0 arithmetic that is cheaper than any exchange (the VALU work hides under the MFMAs).
 // Bit-identical to conv0_kernel + conv_wino_kernel (same fmaf chains, same MFMA accumulation order).
-#include "common.hpp"
+#include "conv_wino_device.hpp"
 
 #include <stdlib.h>
 
@@ -37,21 +37,8 @@
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWaves = 4;
-constexpr unsigned kOob = 0x80000000u;
 constexpr int KQ = 5;                      // k-steps: 20 input channels / 4
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
 
 struct StreamF32Args {
     const float* xs;          // normalised signals, flat [B * P0], preceded by 16 zero bytes
@@ -80,9 +67,7 @@ __global__ __launch_bounds__(kWaves * 64, RS_SF32_BLOCKS) void conv_stream_f32_k
     const int u1 = min(u0 + a.sub_per_wave, a.n_sub);
     if (u0 >= u1) return;
 
-    const __amdgpu_buffer_rsrc_t rs_x =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.xs - 4), 0, a.xs_bytes + 16u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.xs - 4, a.xs_bytes + 16u), rs_y = buffer_rsrc(a.y, a.y_bytes);
     const const_len_ptr clen = as_const_len(a.len);
 
     // ---- resident operands ---------------------------------------------------------------------------
@@ -189,7 +174,8 @@ __global__ __launch_bounds__(kWaves * 64, RS_SF32_BLOCKS) void conv_stream_f32_k
                 const float f = fmaf(w0r[st][2], xs_[2 * k + 3], fmaf(w0r[st][1], xs_[2 * k + 2], fmaf(w0r[st][0], xs_[2 * k + 1], w0r[st][3])));
                 d[k] = vk[k] ? fmaxf(fmaxf(e, f), 0.0f) : 0.0f;
             }
-            const float v[4] = {d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]};
+            float v[4];
+            wino_input_transform<2>(v, d);
 
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -206,10 +192,11 @@ __global__ __launch_bounds__(kWaves * 64, RS_SF32_BLOCKS) void conv_stream_f32_k
             f32x4 o;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float m1 = acc[j][0][q], m2 = acc[j][1][q], m3 = acc[j][2][q], m4 = acc[j][3][q];
-                const float y0 = (m1 + m2) + m3;
-                const float y1 = (m2 - m3) - m4;
-                o[q] = valid ? fmaxf(fmaxf(y0, y1) + bias[j][q], 0.0f) : 0.0f;
+                float m[4], p[1];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) m[k] = acc[j][k][q];
+                wino_output_pool<2>(p, m);
+                o[q] = valid ? fmaxf(p[0] + bias[j][q], 0.0f) : 0.0f;
             }
             const int col = 16 * j + 4 * kq;
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_y,

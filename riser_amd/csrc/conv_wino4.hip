@@ -24,9 +24,7 @@
 // ds_read_b32), the weight slab has six components, a slot = (k-step, component) carries MT * NT MFMAs
 // with MT * NT <= 5 (6 x 4 accumulator registers per 16 x 16 sub-tile), and LDS capacity limits the channel
 // chunk to 16 or 20.  Used for the layers where the matrix pipe is the bound (chosen in rs_model_create).
-#include "common.hpp"
-#include "tile_plan.hpp"
-#include "tile_walk.hpp"
+#include "conv_wino_host.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,17 +33,9 @@
 #include <algorithm>
 #include <utility>
 
+// schedule knobs of the build (DESIGN_HISTORY.md): the defaults are the measured optima
 #ifndef RS_UF_AHEAD
 #define RS_UF_AHEAD 1
-#endif
-#ifndef RS_UF_AHEAD_THIN          // slots of look-ahead x MFMAs per slot for the one- and two-MFMA slots of the thin shapes
-#define RS_UF_AHEAD_THIN 4
-#endif
-#ifndef RS_RD_THIN
-#define RS_RD_THIN 0
-#endif
-#ifndef RS_XF_THIN
-#define RS_XF_THIN 5
 #endif
 #ifndef RS_W4_DIST
 #define RS_W4_DIST 6
@@ -53,25 +43,17 @@
 #ifndef RS_W4_PRIO
 #define RS_W4_PRIO 0
 #endif
-#ifndef RS_W4_STORE_ALWAYS
-#define RS_W4_STORE_ALWAYS 1
-#endif
 
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// the thin shapes' slots (one or two MFMAs): look-ahead of the weight fragments in slots x MFMAs per slot, the component
+// slot that reads the raw rows of the next k-step and the first one that transforms them
+constexpr int kAheadThin = 4, kReadThin = 0, kXformThin = 5;
 
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
+// WinoArgs (conv_wino_host.hpp) without the fused layer-0 members, and with one member no kernel reads: one record for both
+// kernels moved the SGPR spill counts of 49 of these 56 kernels (24 up, by 1 to 5: profiles/f32_device_checks.txt), so the
+// layout stays; launch_wino fills both
 struct Wino4Args {
     const float* x;
     const float* w;        // packed [n_alloc][nch][6][kc] (U0..U5), zero rows beyond c_out
@@ -104,20 +86,11 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
     static_assert(WM * WN == 8 || WM * WN == 4, "8 or 4 waves per workgroup");
     static_assert(KCT == 16 || KCT == 20, "channel chunk");
     constexpr int kThreads = 64 * WM * WN;
-    constexpr int NC = 6;                               // Winograd components
     constexpr int BG = WM * 16 * MT;                    // groups (of 4 conv rows = 2 pooled rows) per tile
     constexpr int BN = WN * 16 * NT;
-    constexpr int S = KCT + 2;
-    constexpr int KQ = KCT / 4;
-    constexpr int PL = (BG + 1) * S;                    // one plane (input rows = p mod 4)
-    constexpr int A_ELEMS = 4 * PL;
-    constexpr int BUF = A_ELEMS + NC * BN * S;
-    constexpr int RPT = (kThreads / KQ) & ~3;           // slab rows per staging pass, a multiple of 4
-    constexpr int A_ROWS = 4 * BG + 2;
-    constexpr int A_PER = (A_ROWS + RPT - 1) / RPT;
-    constexpr int NPP = kThreads / (NC * KQ);
-    constexpr int B_PER = (BN + NPP - 1) / NPP;
-    constexpr unsigned kOob = 0x80000000u;
+    using T = WinoTile<4, BG, BN, KCT, kThreads>;       // planes by input row mod 4, staging passes (conv_wino_device.hpp)
+    constexpr int NC = T::NC, S = T::S, KQ = T::KQ, PL = T::PL, A_ELEMS = T::A_ELEMS, BUF = T::BUF, RPT = T::RPT,
+                  A_ROWS = T::A_ROWS, A_PER = T::A_PER, NPP = T::NPP, B_PER = T::B_PER;
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x;
@@ -139,15 +112,9 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
     const unsigned b_tb = (unsigned)(b_n * a.nch * NC * KCT + 4 * b_rem) * 4u;
     const unsigned a_step = (unsigned)(RPT * a.cp_in) * 4u;
     const unsigned b_step = (unsigned)(NPP * a.nch * NC * KCT) * 4u;
-    const __amdgpu_buffer_rsrc_t rs_x =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_len =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(a.len), 0, a.len_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_bias =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.x, a.x_bytes), rs_w = buffer_rsrc(a.w, a.w_bytes),
+                                 rs_y = buffer_rsrc(a.y, a.y_bytes), rs_len = buffer_rsrc(a.len, a.len_bytes),
+                                 rs_bias = buffer_rsrc(a.bias, a.bias_bytes);
     const const_len_ptr clen = as_const_len(a.len);
 
     u32x4 ra[A_PER], rb[B_PER];
@@ -226,13 +193,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
                 const int b = pr0 / a.P_out;
                 const int t0 = pr0 - b * a.P_out;
                 if (!(b < a.rows_out / a.P_out && t0 + 2 * BG <= a.P_out && t0 >= (clen[b] >> a.shift_out))) break;
-                const int pieces_per_row = BN / 4;
-                for (int f = threadIdx.x; f < 2 * BG * pieces_per_row; f += blockDim.x) {
-                    const int rr = f / pieces_per_row, cc = (f - rr * pieces_per_row) * 4;
-                    const int prow = pr0 + rr, col = tn0 + cc;
-                    if (prow < a.rows_out && col < a.cp_out)
-                        *reinterpret_cast<float4*>(a.y + (int64_t)prow * a.cp_out + col) = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
+                zero_fill_tile<BN>(a.y, pr0, 2 * BG, tn0, a.rows_out, a.cp_out);
             }
             q = order_index();
         }
@@ -307,24 +268,10 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
         // in time, so their weight fragments are read four (two) slots ahead, the raw rows at the first slot of a
         // k-step and transformed behind its last
         constexpr bool THIN = MT * NT <= 2;
-        constexpr int AH = THIN ? (RS_UF_AHEAD_THIN + MT * NT - 1) / (MT * NT) : RS_UF_AHEAD;   // slots of look-ahead of the weight-fragment reads
-        constexpr int RD = THIN ? RS_RD_THIN : 1, XF0 = THIN ? RS_XF_THIN : 3;
+        constexpr int AH = THIN ? (kAheadThin + MT * NT - 1) / (MT * NT) : RS_UF_AHEAD;   // slots of look-ahead of the weight-fragment reads
+        constexpr int RD = THIN ? kReadThin : 1, XF0 = THIN ? kXformThin : 3;
         float uf[AH + 1][NT];                          // weight fragments, ring over the slots in flight
         float v[2][MT][NC];                            // transformed inputs: this k-step / the next one
-        auto xform = [&](float (&o)[NC], const float (&d)[6]) {   // V = B^T d
-#ifdef RS_ABL_NOXFORM                                    // timing experiment only
-            o[0] = d[0], o[1] = d[1], o[2] = d[2], o[3] = d[3], o[4] = d[4], o[5] = d[5];
-#else
-            const float p = fmaf(-4.0f, d[2], d[4]), q = fmaf(-4.0f, d[1], d[3]);
-            const float s2 = d[4] - d[2], t2 = d[3] - d[1];
-            o[0] = fmaf(4.0f, d[0], fmaf(-5.0f, d[2], d[4]));
-            o[1] = p + q;
-            o[2] = p - q;
-            o[3] = fmaf(2.0f, t2, s2);
-            o[4] = fmaf(-2.0f, t2, s2);
-            o[5] = fmaf(4.0f, d[1], fmaf(-5.0f, d[3], d[5]));
-#endif
-        };
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -335,7 +282,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
             for (int j = 0; j < NT; ++j) uf[sl][j] = Bb[((sl % NC) * BN + j * 16) * S + 4 * (sl / NC)];
         });
 #pragma unroll
-        for (int i = 0; i < MT; ++i) xform(v[0][i], dr[i]);      // first k-step of the item: exposed once
+        for (int i = 0; i < MT; ++i) wino_input_transform<4>(v[0][i], dr[i]);      // first k-step of the item: exposed once
 #ifdef RS_ABL_NOFRAG                                    // timing experiment only: no fragment reads after the item's first
 #pragma unroll
         for (int j = 0; j < NT; ++j) uf[AH][j] = uf[0][j];
@@ -359,7 +306,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
 #pragma unroll
                     for (int k = 0; k < 6; ++k) RS_FRAG_A(dr[i][k], Ab[(k & 3) * PL + (i * 16 + (k >> 2)) * S + c0]);
             }
-            if constexpr (xf_next) xform(v[(st + 1) & 1][comp - XF0], dr[comp - XF0]);
+            if constexpr (xf_next) wino_input_transform<4>(v[(st + 1) & 1][comp - XF0], dr[comp - XF0]);
             if constexpr (sl + AH < NSLOTS) {
                 constexpr int nst = (sl + AH) / NC, ncomp = (sl + AH) % NC;
 #pragma unroll
@@ -407,12 +354,9 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
                 } else if constexpr ((u * SPAN) / UNITS == sl)
                     load_unit(U);
                 if constexpr (!DEEP && (u * SPAN) / UNITS + DIST == sl) {
-#if RS_W4_STORE_ALWAYS                                  // unconditional: after the last item the writes land in the idle buffer
-                                                        // (nobody reads it any more); saves a branch per unit: -1.2 % (clock-normalised A/B)
+                    // unconditional (conv_wino_kernel.hpp stores if (has_next)): after the last item the writes land in the idle
+                    // buffer, which nobody reads any more; saves a branch per unit: -1.2 % (clock-normalised A/B)
                     store_unit(U, nbuf);
-#else
-                    if (has_next) store_unit(U, nbuf);
-#endif
                 }
             });
             __builtin_amdgcn_sched_barrier(0);
@@ -444,9 +388,9 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
                 const f32x4 bi = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_bias, (unsigned)col * 4u, 0, 0));
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
-                    f32x4 o0, o1;
+                    f32x4 o[2];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
+                    for (int q = 0; q < 4; ++q) {                      // wino_output_pool<4> + bias, ReLU, length mask
                         const float m0_ = acc[i][j][0][q], m1 = acc[i][j][1][q], m2 = acc[i][j][2][q],
                                     m3 = acc[i][j][3][q], m4 = acc[i][j][4][q], m5 = acc[i][j][5][q];
                         const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
@@ -454,14 +398,14 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
                         const float y1 = fmaf(2.0f, d34, d12);
                         const float y2 = fmaf(4.0f, s34, s12);
                         const float y3 = fmaf(8.0f, d34, d12) + m5;
-                        o0[q] = valid_[i][0] ? fmaxf(fmaxf(y0, y1) + bi[q], 0.0f) : 0.0f;
-                        o1[q] = valid_[i][1] ? fmaxf(fmaxf(y2, y3) + bi[q], 0.0f) : 0.0f;
+                        o[0][q] = valid_[i][0] ? fmaxf(fmaxf(y0, y1) + bi[q], 0.0f) : 0.0f;
+                        o[1][q] = valid_[i][1] ? fmaxf(fmaxf(y2, y3) + bi[q], 0.0f) : 0.0f;
                     }
 #ifdef RS_ABL_NOSTORE
-                    asm volatile("" ::"v"(o0[0]), "v"(o0[1]), "v"(o0[2]), "v"(o0[3]), "v"(o1[0]), "v"(o1[1]), "v"(o1[2]), "v"(o1[3]));
+                    asm volatile("" ::"v"(o[0][0]), "v"(o[0][1]), "v"(o[0][2]), "v"(o[0][3]), "v"(o[1][0]), "v"(o[1][1]), "v"(o[1][2]), "v"(o[1][3]));
 #else
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), rs_y, rowoff_[i][0] + coloff, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rs_y, rowoff_[i][1] + coloff, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[0]), rs_y, rowoff_[i][0] + coloff, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[1]), rs_y, rowoff_[i][1] + coloff, 0, 0);
 #endif
 #pragma unroll
                     for (int q = 0; q < NC; ++q) acc[i][j][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -481,12 +425,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
     }
 }
 
-using KernelFn = void (*)(const Wino4Args);
-
-struct Shape : TileGeom {
-    KernelFn fn[2];        // chunk = 16, 20
-    KernelFn deep[2];      // the same tile with staging loads one item ahead (thin launches), or null
-};
+using Shape = WinoShape<Wino4Args, 2>;     // chunk = 16, 20
 
 #define RS_SHAPE(WM, WN, MT, NT) \
     {{WM, WN, MT, NT}, {conv_wino4_kernel<WM, WN, MT, NT, 16>, conv_wino4_kernel<WM, WN, MT, NT, 20>}, {nullptr, nullptr}}
@@ -515,56 +454,19 @@ const Shape kShapes[] = {
 #undef RS_SHAPE_4
 constexpr int kNumShapes = sizeof(kShapes) / sizeof(kShapes[0]);
 
-size_t lds_bytes(const Shape& s, int kc) {
-    const int bg = s.wm * 16 * s.mt, bn = s.wn * 16 * s.nt;
-    return 2 * (size_t)(4 * (bg + 1) + 6 * bn) * (kc + 2) * sizeof(float);
-}
+// full launches: calibrated on tools/shape_sweep.py (B = 512); the input transform's 12 VALU per MT do not hide behind the
+// MFMAs.  Thin launches: 16 ... 512 reads, every shape, layers 5 - 10 (4 % rms, 15 % worst)
+constexpr WinoCost kCost = {6.0, 12.0, 0.02, 90.0, 23500.0, 71.6, 4.25, -920.0, 0.0062, 0.0124, -467.0, 554.0};
 
-// Full launches (at least one tile per CU): per slot the MFMAs of the two waves of a SIMD, fragment reads, 1/6 of the k-step's
-// input transform (12 VALU per MT, not hidden behind the MFMAs); per item: fixed cost, staging, and the activation slab's trip
-// from L2 / Infinity Cache (the weight slab is an L2 hit).  Calibrated on tools/shape_sweep.py (B = 512); eight-wave shapes.
-double tile_cost(const Shape& s, int kc, int nch) {
-    if (lds_bytes(s, kc) > kConvLdsBudget || s.wm * s.wn != 8) return -1.0;
-    const int bg = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-    const double slots = 6.0 * kc / 4.0;
-    const double staged = ((4.0 * bg + 2) + 6.0 * bnt * 16) * kc * 4.0;
-    const double xslab = (4.0 * bg + 2) * kc * 4.0;
-    const double item = slots * (2.0 * s.mt * s.nt * 32.0 + 6.0 * (s.mt + s.nt) + 12.0 * s.mt) + 900.0 +
-                        0.06 * staged + 0.02 * xslab;
-    return nch * item + 1500.0 + 90.0 * s.mt * s.nt;
-}
-
-// THIN launches (fewer tiles than CUs: 16 ... 100 reads in the late layers): a least-squares fit over tools/shape_sweep.py at
-// 16 ... 512 reads, every shape, layers 5 - 10 (4 % rms, 15 % worst).  Per slot the MFMAs of a SIMD's waves add up; the
-// other instructions of a slot do not depend on the waves per SIMD; staged bytes cost more the more CUs stream (fill).
-// per_cu: workgroups of a four-wave shape resident on one CU (two: their waves share the SIMDs like an eight-wave
-// workgroup's).  kThinLaunch: launch + first / last tile effects of the same fit (for the comparison with conv_small_f32).
-constexpr double kThinLaunch = 23500.0;
-double thin_tile_cost(const Shape& s, int kc, int nch, int per_cu, double fill) {
-    if (lds_bytes(s, kc) * per_cu > kConvLdsBudget) return -1.0;
-    const int bg = s.wm * 16 * s.mt, bnt = s.wn * s.nt;
-    const double slots = 6.0 * kc / 4.0;
-    const double staged = ((4.0 * bg + 2) + 6.0 * bnt * 16) * kc * 4.0 * per_cu;
-    const double wps = s.wm * s.wn * per_cu / 4.0;
-    const double item = slots * (wps * s.mt * s.nt * 32.0 + 71.6 + 4.25 * (s.mt + s.nt)) - 920.0 + staged * (0.0062 + 0.0124 * fill);
-    return nch * item - 467.0 + 554.0 * s.mt * s.nt;
-}
-
-// the family as plan_tiles sees it (tile_plan.hpp), for a layer of nch chunks of kc channels.  Row unit: GROUPS of four conv rows.
-// A forced or tuned shape need only fit the LDS: the four-wave entries, which no full-launch search picks, can be pinned.
-auto family(int kc, int nch) {
-    return tile_family(
-        kNumShapes, [](int k) -> const TileGeom& { return kShapes[k]; }, [=](int k) { return tile_cost(kShapes[k], kc, nch); },
-        [=](int k, int per_cu, double fill) { return thin_tile_cost(kShapes[k], kc, nch, per_cu, fill); },
-        [=](int k) { return lds_bytes(kShapes[k], kc) <= kConvLdsBudget; });
-}
+// row unit: GROUPS of four conv rows
+auto family(int kc, int nch) { return wino_family<4>(kShapes, kNumShapes, kCost, kc, nch); }
 
 }  // namespace
 
 int conv_wino4_max_bn() { return 256; }
 int conv_wino4_num_shapes() { return kNumShapes; }
 bool conv_wino4_shape_ok(const ConvLayerDev& L, int k) {
-    return k >= 0 && k < kNumShapes && (L.plan.kc == 16 || L.plan.kc == 20) && family(L.plan.kc, L.plan.nch).can_run(k);
+    return k >= 0 && k < kNumShapes && wino_chunk_index<Shape>(L.plan.kc) >= 0 && family(L.plan.kc, L.plan.nch).can_run(k);
 }
 
 // planner's estimate (SIMD cycles) of one launch with the best tile shape for this chunk size: lets
@@ -572,93 +474,14 @@ bool conv_wino4_shape_ok(const ConvLayerDev& L, int k) {
 double conv_wino4_plan_cost(int64_t groups, int n16, int kc, int nch, int num_cu) {
     return choose_tile(family(kc, nch), groups, n16, num_cu, false).cost;
 }
-
-// estimate of one launch INCLUDING its launch cost where the thin-launch fit applies (*thin_out), for the choice between
-// this kernel and conv_small_f32 (whose fit includes its launch as well)
 double conv_wino4_launch_cost(int64_t groups, int n16, int kc, int nch, int num_cu, bool* thin_out) {
-    const TileChoice c = choose_tile(family(kc, nch), groups, n16, num_cu);
-    if (thin_out) *thin_out = c.thin;
-    return c.thin ? c.cost + kThinLaunch : c.cost;
+    return wino_launch_cost(family(kc, nch), groups, n16, num_cu, kCost, thin_out);
 }
 
 int launch_conv_wino4(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len, int B, int P_in,
                       int layer_index, int num_cu, int check_dead, hipStream_t st, int* bm_out, int* bn_out) {
-    const ConvPlan& p = L.plan;
-    if (p.kc != 16 && p.kc != 20) {
-        set_error("conv_wino4: unsupported channel chunk %d", p.kc);
-        return RS_ERR_ARG;
-    }
-    const int64_t rows64 = (int64_t)B * P_in;
-    const int64_t xb = rows64 * L.cp_in * 4, wb = (int64_t)p.n_alloc * p.nch * 6 * p.kc * 4,
-                  yb = rows64 / 2 * L.cp_out * 4;
-    if (rows64 > 0x7fffffff || xb >= 0x80000000LL || wb >= 0x80000000LL || yb >= 0x80000000LL) {
-        set_error("conv_wino4: batch too large for the 2 GiB buffer window, split it");
-        return RS_ERR_ARG;
-    }
-    const int n16 = round_up(L.c_out, 16) / 16;
-    const int64_t groups = (rows64 + 3) / 4;
-    const TilePlan plan = plan_tiles(family(p.kc, p.nch), groups, n16, num_cu,
-                                     {L.hooks->force_wino4, layer_index, tuned_pick(L.force_shape, L.tuned, rows64)},
-                                     {!L.hooks->no_tail_split, L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.97, true});
-    if (!plan.n_parts) {
-        set_error("conv_wino4: no tile shape fits (kc=%d)", p.kc);
-        return RS_ERR_ARG;
-    }
-    Wino4Args a;
-    a.x = d_x;
-    a.w = static_cast<const float*>(L.d_w);
-    a.bias = L.d_bias;
-    a.y = d_y;
-    a.len = d_len;
-    a.x_bytes = (unsigned)xb;
-    a.w_bytes = (unsigned)wb;
-    a.y_bytes = (unsigned)yb;
-    a.y_row_bytes = (unsigned)L.cp_out * 4u;
-    a.len_bytes = (unsigned)B * 4u;
-    a.bias_bytes = (unsigned)p.n_alloc * 4u;
-    a.rows_in = (int)rows64;
-    a.rows_out = (int)(rows64 / 2);
-    a.n_groups = (int)groups;
-    a.P_out = P_in / 2;
-    a.inv_P_out = 1.0f / (float)a.P_out;
-    a.cp_in = L.cp_in;
-    a.cp_out = L.cp_out;
-    a.nch = p.nch;
-    a.shift_out = layer_index + 1;
-    // one launch over the row tiles [m_base, m_base + n_mtiles x BG) of shape sh
-    auto launch_part = [&](const Shape& sh, int m_base, int n_mtiles, int wg_per_cu) -> int {
-        const int BN = sh.wn * 16 * sh.nt;
-        const int n_ntiles = (n16 * 16 + BN - 1) / BN;
-        const int64_t tiles = (int64_t)n_mtiles * n_ntiles;
-        const int slots_ = num_cu * wg_per_cu;
-        const unsigned grid = (unsigned)std::min<int64_t>(tiles, slots_);
-        a.walk = plan_walk(n_mtiles, n_ntiles, grid, slots_, 4.0 * sh.wm * 16 * sh.mt, 6.0 * BN, check_dead,
-                           !L.hooks->no_rect_order);
-        a.walk.m_base = m_base;
-        KernelFn fn = sh.fn[p.kc == 16 ? 0 : 1];
-        if (KernelFn d = sh.deep[p.kc == 16 ? 0 : 1]; d && !L.hooks->no_deep_staging) fn = d;
-        RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)kConvLdsBudget));
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * sh.wm * sh.wn), lds_bytes(sh, p.kc), st, a);
-        RS_HIP(hipGetLastError());
-        return RS_OK;
-    };
-    const Shape& h = kShapes[plan.part[0].shape];
-    if (plan.n_parts == 2 && L.hooks->tail_debug) {
-        const Shape& t = kShapes[plan.part[1].shape];
-        fprintf(stderr, "[tail-split] layer %d: head %dx%dx%dx%d x %d row tiles, tail %dx%dx%dx%d (%d per CU); planned %.0f vs %.0f cycles\n",
-                layer_index, h.wm, h.wn, h.mt, h.nt, plan.part[0].n_mtiles, t.wm, t.wn, t.mt, t.nt, plan.part[1].per_cu, plan.cost,
-                plan.single_cost);
-    }
-    for (int i = 0; i < plan.n_parts; ++i) {
-        const TilePart& part = plan.part[i];
-        const int rc = launch_part(kShapes[part.shape], part.m_base, part.n_mtiles, part.per_cu);
-        if (rc != RS_OK) return rc;
-    }
-    const int BG = h.bm(), BN = h.bn();       // a split reports the head's shape
-    if (bm_out) *bm_out = 4 * BG;           // reported in conv rows, like the other kernels
-    if (bn_out) *bn_out = BN;
-    return RS_OK;
+    return launch_wino<4>("conv_wino4", kShapes, kNumShapes, kCost, L.hooks->force_wino4, L, d_x, d_y, d_len, B, P_in, layer_index,
+                          num_cu, check_dead, st, bm_out, bn_out);
 }
 
 }  // namespace rs

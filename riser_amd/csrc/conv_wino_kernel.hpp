@@ -2,62 +2,14 @@
 // shapes of full launches, the layer-0 fold, planner and launcher) and conv_wino_thin.hip (the thin-launch forms: four-wave
 // workgroups and loads one item ahead) - two translation units, so that the two halves of the instantiations compile side by side.
 #pragma once
-#include "common.hpp"
-#include "tile_walk.hpp"
-#include <stdio.h>
+#include "conv_wino_host.hpp"
 #include <stdlib.h>
 #include <string.h>
-#include <algorithm>
 #include <utility>
 
 namespace rs {
 
-struct WinoArgs {
-    const float* x;
-    const float* w;        // packed [n_alloc][nch][4][kc] (U0..U3), zero rows beyond c_out
-    const float* bias;     // [n_alloc]
-    float* y;
-    const int32_t* len;
-    unsigned x_bytes;      // size of the activation buffer x (rows_in * cp_in floats), < 2^31
-    unsigned w_bytes;      // size of the packed weights, < 2^31
-    unsigned y_bytes;      // size of the output buffer (rows_out * cp_out floats), < 2^31
-    unsigned y_row_bytes;  // cp_out * 4
-    unsigned len_bytes;    // B * 4
-    unsigned bias_bytes;   // n_alloc * 4
-    int rows_in;           // B * P_in
-    int rows_out;          // B * P_out
-    int P_out;
-    float inv_P_out;
-    int cp_in, cp_out;
-    int nch;
-    int shift_out;         // valid output rows of read b: len[b] >> shift_out
-    WalkArgs walk;         // tile grid, order and dead-tile flag (tile_walk.hpp)
-    // FUSE0 (layer 1 only): the input rows are not read from x but computed on the fly from the
-    // normalised signal - ConvNet layer 0 (C_in = 1: 3 FMAs per output) folded into the staging
-    const float* xs;       // normalised signals, flat [B * P0] (row pitch == P0, zero beyond each read's length),
-                           // preceded by >= 16 readable bytes of zeros
-    unsigned xs_bytes;
-    const float* w0;       // layer 0: [cp_in][4] = (w0, w1, w2, bias)
-    int n_reads;
-};
-
 namespace {
-
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// compile-time loop: the body sees its index as a constant expression, so every register-array
-// index in the slot loop is static whatever hipcc's unroll heuristics decide
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
 
 // DEEP (thin launches, see conv_wino4.hip): the staging loads of an item are issued ONE ITEM earlier and stay in registers
 // across the barrier.  Four-wave workgroups (one wave per SIMD) for launches of fewer tiles than CUs.  Same MFMA sequence
@@ -71,18 +23,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
     constexpr int kThreads = 64 * WM * WN;
     constexpr int BMP = WM * 16 * MT;                  // pooled rows per tile
     constexpr int BN = WN * 16 * NT;
-    constexpr int S = KCT + 2;
-    constexpr int KQ = KCT / 4;
-    constexpr int PL = (BMP + 1) * S;                  // one parity plane
-    constexpr int A_ELEMS = 2 * PL;
-    constexpr int BUF = A_ELEMS + 4 * BN * S;
-    // staging passes: a pass of the workgroup covers RPT slab rows x KQ 16-byte units of the X slab,
-    // or NPP output channels x 4 components x KQ units of the weight slab
-    constexpr int RPT = (kThreads / KQ) & ~1;
-    constexpr int A_ROWS = 2 * BMP + 2;
-    constexpr int A_PER = (A_ROWS + RPT - 1) / RPT;
-    constexpr int NPP = kThreads / (4 * KQ);
-    constexpr int B_PER = (BN + NPP - 1) / NPP;
+    using T = WinoTile<2, BMP, BN, KCT, kThreads>;     // parity planes, staging passes (conv_wino_device.hpp)
+    constexpr int S = T::S, KQ = T::KQ, PL = T::PL, A_ELEMS = T::A_ELEMS, BUF = T::BUF, RPT = T::RPT, A_ROWS = T::A_ROWS,
+                  A_PER = T::A_PER, NPP = T::NPP, B_PER = T::B_PER;
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
     const int tid = threadIdx.x;
@@ -111,17 +54,9 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
     const unsigned b_tb = (unsigned)(b_n * a.nch * 4 * KCT + 4 * b_rem) * 4u;
     const unsigned a_step = (unsigned)(RPT * a.cp_in) * 4u;
     const unsigned b_step = (unsigned)(NPP * a.nch * 4 * KCT) * 4u;
-    constexpr unsigned kOob = 0x80000000u;             // >= num_records of either buffer (host checks)
-    const __amdgpu_buffer_rsrc_t rs_x =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, a.w_bytes, 0x00020000);
-
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_len =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(a.len), 0, a.len_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_bias =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.x, a.x_bytes), rs_w = buffer_rsrc(a.w, a.w_bytes),
+                                 rs_y = buffer_rsrc(a.y, a.y_bytes), rs_len = buffer_rsrc(a.len, a.len_bytes),
+                                 rs_bias = buffer_rsrc(a.bias, a.bias_bytes);
 
     // FUSE0: input row g of this layer = output row g of layer 0 = relu(max(conv(x)[2t], conv(x)[2t+1]) + b)
     // of read b = g / P_in at t = g % P_in, computed from the four samples x[2g-1 .. 2g+2] of the FLAT
@@ -131,8 +66,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
     // (the descriptor starts 16 bytes before the first sample - the caller guarantees four zero floats
     // there - so the offset of x[2g-1] is never negative: a load that STARTS out of range returns zeros
     // for all four dwords, including the three in-range ones)
-    const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(FUSE0 ? a.xs - 4 : a.x), 0, FUSE0 ? a.xs_bytes + 16u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_s = buffer_rsrc(FUSE0 ? a.xs - 4 : a.x, FUSE0 ? a.xs_bytes + 16u : 0u);
     const int P_in = 2 * a.P_out;
     const const_len_ptr clen = as_const_len(a.len);
     f32x4 w0r[4];
@@ -244,13 +178,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
                 const int b = tm0 / a.P_out;
                 const int t0 = tm0 - b * a.P_out;
                 if (!(t0 + BMP <= a.P_out && t0 >= (clen[b] >> a.shift_out))) break;
-                const int pieces_per_row = BN / 4;
-                for (int f = threadIdx.x; f < BMP * pieces_per_row; f += blockDim.x) {
-                    const int rr = f / pieces_per_row, cc = (f - rr * pieces_per_row) * 4;
-                    const int prow = tm0 + rr, col = tn0 + cc;
-                    if (prow < a.rows_out && col < a.cp_out)
-                        *reinterpret_cast<float4*>(a.y + (int64_t)prow * a.cp_out + col) = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
+                zero_fill_tile<BN>(a.y, tm0, BMP, tn0, a.rows_out, a.cp_out);
             }
             q = order_index();
         }
@@ -368,20 +296,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
                 constexpr int st = sl >> 2, comp = sl & 3;
                 if constexpr (comp == 0) {
 #pragma unroll
-                    for (int i = 0; i < MT; ++i) {
-                        const float d0 = dr[i][0], d1 = dr[i][1], d2 = dr[i][2], d3 = dr[i][3];
-#ifdef RS_ABL_NOXFORM                                      // timing experiment only
-                        v[i][0] = d0;
-                        v[i][1] = d1;
-                        v[i][2] = d2;
-                        v[i][3] = d3;
-#else
-                        v[i][0] = d0 - d2;
-                        v[i][1] = d1 + d2;
-                        v[i][2] = d2 - d1;
-                        v[i][3] = d1 - d3;
-#endif
-                    }
+                    for (int i = 0; i < MT; ++i) wino_input_transform<2>(v[i], dr[i]);
                 }
                 if constexpr (comp == RD && st + 1 < KQ) {
                     constexpr int c0 = 4 * (st + 1);
@@ -409,7 +324,6 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
                             acc[i][j][comp] = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[sl % (AH + 1)][j], v[i][comp],
                                                                                    acc[i][j][comp], 0, 0, 0);
                     }
-#ifndef RS_WINO_NO_SGB2
                 {   // one LDS read in the shadow of each of the first MFMAs, so the next slot's fragments are
                     // in flight early without a read burst ahead of the MFMAs
                     constexpr int n_rd = (sl + AH < NSLOTS ? NT : 0) + ((comp == RD && st + 1 < KQ) ? 2 * MT : 0);
@@ -420,7 +334,6 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
                     });
                     if constexpr (MT * NT - n_pair > 0) __builtin_amdgcn_sched_group_barrier(0x008, MT * NT - n_pair, 0);
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 static_for<UNITS>([&](auto U) {
                     constexpr int u = decltype(U)::value;
@@ -499,7 +412,7 @@ __global__ __launch_bounds__(512) void conv_wino_kernel(const WinoArgs a) {
                 for (int i = 0; i < MT; ++i) {
                     f32x4 o4;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
+                    for (int q = 0; q < 4; ++q) {                      // wino_output_pool<2> + bias, ReLU, length mask
                         const float m1 = acc[i][j][0][q], m2 = acc[i][j][1][q], m3 = acc[i][j][2][q],
                                     m4 = acc[i][j][3][q];
                         const float y0 = (m1 + m2) + m3;

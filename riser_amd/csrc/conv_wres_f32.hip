@@ -19,9 +19,9 @@
 //     and cover each other's waits;
 //   * the chunk's slots run as in the tiled kernels: raw-row reads, input transform, weight fragments one slot ahead, MFMAs.
 // Per accumulator the MFMA sequence is the tiled kernels' (chunks ascending, k-steps ascending, the same operands in the
-// same positions; the first k-step of a step accumulates onto a literal zero), the transforms and the epilogue are theirs:
-// results are byte-identical (tests/test_gpu_f32_wres.py).
-#include "common.hpp"
+// same positions; the first k-step of a step accumulates onto a literal zero), the plane layout, the transforms and the
+// epilogue's arithmetic are theirs (conv_wino_device.hpp): results are byte-identical (tests/test_gpu_f32_wres.py).
+#include "conv_wino_device.hpp"
 #include "tile_plan.hpp"
 
 #include <stdlib.h>
@@ -32,21 +32,8 @@
 namespace rs {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWaves = 8;
 constexpr int kKc = 16;                     // the channel chunk this kernel is instantiated for
-constexpr unsigned kOob = 0x80000000u;
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
 
 struct WresF32Args {
     const float* x;
@@ -68,18 +55,15 @@ struct WresF32Args {
 
 // geometry of one instantiation, shared by the kernel and the host's LDS arithmetic
 template <int M, int NT, int KCT>
-struct Geom {
-    static constexpr int NC = M + 2;                   // Winograd components = raw inputs d0 .. d(M+1) of a unit
-    static constexpr int NP = M;                       // planes of the image: input row s of the step lives in plane s % NP
+struct Geom : WinoGeom<M, KCT> {                       // NC, NP, S, KQ and the 17-row plane: conv_wino_device.hpp
+    using W = WinoGeom<M, KCT>;
     static constexpr int ROWS = 8 * M;                 // pooled rows of a step (16 units of M / 2)
     static constexpr int A_ROWS = 16 * M + 2;          // input rows of a step
-    static constexpr int S = KCT + 2;
-    static constexpr int KQ = KCT / 4;
-    static constexpr int PL = 17 * S;                  // one plane
-    static constexpr int IMG = NP * PL;                // one wave's image of one chunk
+    static constexpr int PL = W::PL16;                 // one plane
+    static constexpr int IMG = W::IMG16;               // one wave's image of one chunk
     static constexpr int BN = 16 * NT;
-    static constexpr int WCH = NC * BN * S;            // one chunk of the resident weights
-    static constexpr int NL = (A_ROWS * KQ + 63) / 64; // 16-byte loads per lane and chunk
+    static constexpr int WCH = W::NC * BN * W::S;      // one chunk of the resident weights
+    static constexpr int NL = (A_ROWS * W::KQ + 63) / 64; // 16-byte loads per lane and chunk
     static size_t lds_bytes(int nch) { return ((size_t)BN + (size_t)nch * WCH + (size_t)kWaves * IMG) * sizeof(float); }
 };
 
@@ -100,15 +84,9 @@ __global__ __launch_bounds__(kWaves * 64, BLOCKS) void conv_wres_f32_kernel(cons
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, kq = lane >> 4;
 
-    const __amdgpu_buffer_rsrc_t rs_x =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_len =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(a.len), 0, a.len_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_bias =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, a.bias_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(a.x, a.x_bytes), rs_w = buffer_rsrc(a.w, a.w_bytes),
+                                 rs_y = buffer_rsrc(a.y, a.y_bytes), rs_len = buffer_rsrc(a.len, a.len_bytes),
+                                 rs_bias = buffer_rsrc(a.bias, a.bias_bytes);
     const const_len_ptr clen = as_const_len(a.len);
 
     const int gw = blockIdx.x * kWaves + wave;
@@ -187,23 +165,6 @@ __global__ __launch_bounds__(kWaves * 64, BLOCKS) void conv_wres_f32_kernel(cons
     // a slot of one or two MFMAs is shorter than an LDS round trip: its weight fragments are read further ahead
     constexpr int AH = NT >= 4 ? 1 : NT == 3 ? 2 : (4 + NT - 1) / NT;
     constexpr int RD = 1, XF = NC - 1;                 // component slots that read / transform the raw rows of the next k-step
-    auto xform = [&](float (&o)[NC], const float (&d)[NC]) {
-        if constexpr (M == 2) {                        // conv_wino_kernel.hpp
-            o[0] = d[0] - d[2];
-            o[1] = d[1] + d[2];
-            o[2] = d[2] - d[1];
-            o[3] = d[1] - d[3];
-        } else {                                       // conv_wino4.hip: V = B^T d
-            const float p = fmaf(-4.0f, d[2], d[4]), q = fmaf(-4.0f, d[1], d[3]);
-            const float s2 = d[4] - d[2], t2 = d[3] - d[1];
-            o[0] = fmaf(4.0f, d[0], fmaf(-5.0f, d[2], d[4]));
-            o[1] = p + q;
-            o[2] = p - q;
-            o[3] = fmaf(2.0f, t2, s2);
-            o[4] = fmaf(-2.0f, t2, s2);
-            o[5] = fmaf(4.0f, d[1], fmaf(-5.0f, d[3], d[5]));
-        }
-    };
     auto run_chunk = [&](auto FIRST, const float* Bb) {
         constexpr bool first = decltype(FIRST)::value;   // first chunk of a step: accumulate onto zero
         float dr[NC];
@@ -216,7 +177,7 @@ __global__ __launch_bounds__(kWaves * 64, BLOCKS) void conv_wres_f32_kernel(cons
 #pragma unroll
             for (int j = 0; j < NT; ++j) uf[sl][j] = Bb[((sl % NC) * BN + j * 16) * S + 4 * (sl / NC)];
         });
-        xform(v[0], dr);
+        wino_input_transform<M>(v[0], dr);
         static_for<NSLOTS>([&](auto SL) {
             constexpr int sl = decltype(SL)::value;
             constexpr int st = sl / NC, comp = sl % NC;
@@ -227,7 +188,7 @@ __global__ __launch_bounds__(kWaves * 64, BLOCKS) void conv_wres_f32_kernel(cons
 #pragma unroll
                 for (int k = 0; k < NC; ++k) dr[k] = Ab[(k % NP) * PL + (k / NP) * S + c0];
             }
-            if constexpr (xf_next) xform(v[(st + 1) & 1], dr);
+            if constexpr (xf_next) wino_input_transform<M>(v[(st + 1) & 1], dr);
             if constexpr (sl + AH < NSLOTS) {
                 constexpr int nst = (sl + AH) / NC, ncomp = (sl + AH) % NC;
 #pragma unroll
@@ -325,33 +286,19 @@ __global__ __launch_bounds__(kWaves * 64, BLOCKS) void conv_wres_f32_kernel(cons
                 const unsigned coloff = col < a.cp_out ? (unsigned)col * 4u : kOob;
                 f32x4 bi = *reinterpret_cast<const f32x4*>(bl + col);
                 asm volatile("" : "+v"(bi));           // read here, for every lane: not inside the length mask's branches
-                if constexpr (M == 2) {
-                    f32x4 o4;
+                f32x4 o[H];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float m1 = acc[j][0][q], m2 = acc[j][1][q], m3 = acc[j][2][q], m4 = acc[j][3][q];
-                        const float y0 = (m1 + m2) + m3;
-                        const float y1 = (m2 - m3) - m4;
-                        o4[q] = valid_[0] ? fmaxf(fmaxf(y0, y1) + bi[q], 0.0f) : 0.0f;
-                    }
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o4), rs_y, rowoff_[0] + coloff, 0, 0);
-                } else {
-                    f32x4 o0, o1;
+                for (int q = 0; q < 4; ++q) {
+                    float m[NC], p[H];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float m0_ = acc[j][0][q], m1 = acc[j][1][q], m2 = acc[j][2][q], m3 = acc[j][3][q],
-                                    m4 = acc[j][NC - 2][q], m5 = acc[j][NC - 1][q];
-                        const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                        const float y0 = (m0_ + s12) + s34;
-                        const float y1 = fmaf(2.0f, d34, d12);
-                        const float y2 = fmaf(4.0f, s34, s12);
-                        const float y3 = fmaf(8.0f, d34, d12) + m5;
-                        o0[q] = valid_[0] ? fmaxf(fmaxf(y0, y1) + bi[q], 0.0f) : 0.0f;
-                        o1[q] = valid_[H - 1] ? fmaxf(fmaxf(y2, y3) + bi[q], 0.0f) : 0.0f;
-                    }
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), rs_y, rowoff_[0] + coloff, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rs_y, rowoff_[H - 1] + coloff, 0, 0);
+                    for (int k = 0; k < NC; ++k) m[k] = acc[j][k][q];
+                    wino_output_pool<M>(p, m);
+#pragma unroll
+                    for (int h = 0; h < H; ++h) o[h][q] = valid_[h] ? fmaxf(p[h] + bi[q], 0.0f) : 0.0f;
                 }
+#pragma unroll
+                for (int h = 0; h < H; ++h)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[h]), rs_y, rowoff_[h] + coloff, 0, 0);
             }
         }
         t0 += ROWS;

@@ -21,7 +21,7 @@
 //
 // rs_gconv_set_mode(m, RS_BF16X3) runs every conv with c_in > 4 on gconv_tile_x3_kernel instead (csrc/gconv_x3.hip: split
 // precision on the bf16 MFMA, the same plan, grid, buffers and epilogue); the other two kernels serve both modes.
-#include "common.hpp"
+#include "device_prelude.hpp"
 #include "family/head.hpp"
 #include "family/host.hpp"
 #include "gconv/plan.hpp"
@@ -37,7 +37,6 @@ namespace {
 
 using namespace gconv;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void gconv_lengths_kernel(const int32_t* __restrict__ len, int B, int ld, int n_pools,
                                                             int32_t* __restrict__ table) {
