@@ -41,8 +41,9 @@ struct PrepArgs {
     float lim;
 };
 
+// 8 waves per SIMD by registers: short cutoffs leave LDS for four workgroups per CU, and the registers must too
 template <bool RAW16>
-__global__ __launch_bounds__(kThreads) void retrain_prep_kernel(PrepArgs a) {
+__global__ __launch_bounds__(kThreads, 8) void retrain_prep_kernel(PrepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float xs[];
     __shared__ __attribute__((aligned(16))) unsigned hist[kWaves * 256];
     __shared__ unsigned red[kWaves];

@@ -4,6 +4,16 @@
 // bin of a wave's first counting lane (and then the next one's) is counted once, by ballot, and only what is left goes through LDS
 // atomics.  The two middle values of an even n are adjacent order statistics: the last pass tells whether rank k + 1 carries the
 // same value, and if not it is the smallest value above - one min reduction, not a second selection.
+// NaN: np.median answers NaN as soon as one of the n values is a NaN, for an odd and an even n alike.  A NaN's image lies beyond
+// those of the infinities (Bits<T>::is_nan), so it can only have been counted into the outermost bins of the first pass
+// (Bits<T>::kNanBinLo and below, kNanBinHi and above), which hold nothing else but the infinities and, in float32 and float64, the
+// finite values of the largest exponent(s).  The counting loop stays as it is; where the first pass's totals show a key in one of
+// those bins - no signal does - block_median looks at every key once more (block_has_nan, n keys) and answers NaN if one is a
+// NaN's image.  With a NaN median every |x - med| is NaN, so the MAD's select answers NaN in the same way, as it does for an
+// infinite median (inf - inf).
+// Signed zeros: np.median is np.mean of the middle value(s), a sum that starts from +0.0, so a median that is a zero is +0.0
+// whatever the signs of the zeros in the read - also for an odd n, and for two middle values of -0.0.  block_median adds in that
+// order (float_bits.hpp on why the image's own order of the two zeros does not matter).
 #pragma once
 
 #include "float_arith.hpp"
@@ -12,9 +22,11 @@
 
 namespace rs {
 
-// k-th smallest (0-based) of the n keys key(0 .. n-1); every thread returns it, and next_same = rank k + 1 holds it too
+// k-th smallest (0-based) of the n keys key(0 .. n-1); every thread returns it, and next_same = rank k + 1 holds it too.
+// nan_bins (workgroup-uniform): a key was counted into one of the bins that a NaN's image falls into
 template <class T, int THREADS, class KeyF>
-__device__ typename Bits<T>::type block_select(KeyF key, int n, int k, unsigned* hist, int tid, bool& next_same) {
+__device__ typename Bits<T>::type block_select(KeyF key, int n, int k, unsigned* hist, int tid, bool& next_same,
+                                               bool& nan_bins) {
     typedef typename Bits<T>::type K;
     const int lane = tid & 63, wave = tid >> 6;
     unsigned* mine = hist + wave * 256;
@@ -57,6 +69,13 @@ __device__ typename Bits<T>::type block_select(KeyF key, int n, int k, unsigned*
             c[2] += (int)h.z;
             c[3] += (int)h.w;
         }
+        if (pass == 0) {                                              // every wave holds the same totals
+            bool outer = false;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                outer |= c[j] != 0 && (4 * lane + j <= Bits<T>::kNanBinLo || 4 * lane + j >= Bits<T>::kNanBinHi);
+            nan_bins = __ballot(outer) != 0;
+        }
         int bin, rest;
         wave_find_rank(c, lane, k, bin, rest, count);
         prefix = (prefix << 8) | (K)bin;
@@ -67,13 +86,28 @@ __device__ typename Bits<T>::type block_select(KeyF key, int n, int k, unsigned*
     return prefix;
 }
 
-// np.median of the n values of dtype T whose images are key(i); red: THREADS / 64 keys
+// one of the n keys is the image of a NaN; every thread returns it.  flag: one LDS word that no thread is still reading
+template <class T, int THREADS, class KeyF>
+__device__ bool block_has_nan(KeyF key, int n, typename Bits<T>::type* flag, int tid) {
+    bool nan = false;
+    for (int i = tid; i < n; i += THREADS) nan |= Bits<T>::is_nan(key(i));
+    if (tid == 0) *flag = 0;
+    __syncthreads();
+    if (__ballot(nan) && (tid & 63) == 0) *flag = 1;                  // every writer writes the same word
+    __syncthreads();
+    const bool any = *flag != 0;
+    __syncthreads();                                                  // all have read: the caller may use the word again
+    return any;
+}
+
+// np.median of the n values of dtype T whose images are key(i), NaN if one of them is a NaN; red: THREADS / 64 keys
 template <class T, int THREADS, class KeyF>
 __device__ T block_median(KeyF key, int n, unsigned* hist, typename Bits<T>::type* red, int tid) {
     typedef typename Bits<T>::type K;
-    bool same;
-    const K k_lo = block_select<T, THREADS>(key, n, (n - 1) >> 1, hist, tid, same);
-    const T lo = Bits<T>::value(k_lo);
+    bool same, nan_bins;
+    const K k_lo = block_select<T, THREADS>(key, n, (n - 1) >> 1, hist, tid, same, nan_bins);
+    if (nan_bins && block_has_nan<T, THREADS>(key, n, red, tid)) return (T)__builtin_nanf("");      // workgroup-uniform
+    const T lo = Arith<T>::add((T)0, Bits<T>::value(k_lo));          // np.mean's sum starts from +0.0: -0.0 becomes +0.0
     if (n & 1) return lo;
     K k_hi = k_lo;
     if (!same) {                                                      // workgroup-uniform; rank n / 2: the smallest key above

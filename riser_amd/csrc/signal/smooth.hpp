@@ -4,7 +4,10 @@
 // replacement needs the one before it: every thread writes the elements that are no outliers, and the first element of a run of
 // outliers walks its run.  NaN is no outlier, +-inf is one, and a NaN replacement passes the clip.  With a zero denom every element
 // off the median is +-inf, a run can span the whole read and one lane walks it: rare (more than half of the samples equal) and
-// accepted.
+// accepted.  Input edges (tests/test_float_edges.py): a NaN med or denom (a NaN sample, or an infinite median: radix_select.hpp)
+// makes every y NaN, no element is an outlier and the row is NaN; an infinite sample beside a finite med and denom is an outlier,
+// (prev + inf) / 2 clips to +-lim and index 0 / n - 1 copy their neighbour unclipped; an infinite denom (an overflowing 1.4826 *
+// mad) gives +-0.0 and, with an infinite MAD, NaN off the median; subnormal y are kept, nothing is flushed.
 #pragma once
 
 #include "float_arith.hpp"

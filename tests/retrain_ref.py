@@ -44,7 +44,7 @@ def same_bits(a, b):
     if a.shape != b.shape or a.dtype != b.dtype:
         return False
     na, nb = np.isnan(a), np.isnan(b)
-    iv = a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+    iv = a.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
     jv = b.view(iv.dtype)
     return bool(np.array_equal(na, nb) and np.array_equal(iv[~na], jv[~nb]))
 
