@@ -618,6 +618,52 @@ RS_API int rs_retrain_prepare(const void* d_sig, int elem_bytes, const int64_t* 
                               const double* d_calib, int B, const int32_t* cutoffs, int n_cut, float outlier_lim,
                               const int64_t* d_rows, float* const* d_out, double* d_stats, void* stream);
 
+/* Added after ABI 2.9, rs_version unchanged: training of the ConvNet class every shipped config uses (riser/nets/cnn.py:12-18,
+ * 43-65 at depth 1, every kernel 3, the `gap_fc` head, two classes; riser/train.py:31-80,197-198): forward, cross-entropy with
+ * mean reduction, backward and torch.optim.Adam, fp32, on the device (csrc/train.hip).  A batch is B reads of ONE length L
+ * (the reference's datasets are [N, cutoff] tensors); d_x is fp32 [B, ld], ld >= L, d_labels int32 [B] in {0, 1}.
+ *
+ * rs_train_create takes the layer table (rs_gconv_conv, k = 3, weights [c_out][c_in][3]) and the Linear [2, c_last]; the
+ * parameters then live on the device as one flat fp32 vector with its gradient and the two Adam moments, and no weight
+ * crosses the bus inside a step.  device < 0 makes a handle WITHOUT device memory: the plan functions and every argument
+ * check below answer for it, and a call that would launch is refused with RS_ERR_ARG after its checks.
+ * rs_train_workspace_bytes: the bytes one call of B reads of L samples needs - per layer the pooled rows, their gradient and
+ * one selector byte per pooled element, the head's buffers, and the partial tiles of the sliced weight gradients; 0 for a
+ * null handle or an L that leaves no row behind the last pool.  rs_train_max_batch: the largest B whose every buffer stays
+ * inside the 2 GiB window.  rs_train_slice_plan: into how many slices of how many positions layer `layer`'s weight-gradient
+ * contraction over B * (L >> layer) positions is cut - a function of (B, L, layer shape) alone, so the sums are the same
+ * bits on every device and run.
+ * rs_train_forward_backward writes d_out[0] = loss, d_out[1] = reads whose argmax equals their label, d_out[2 + 2 b + j] =
+ * logit j of read b, leaves the gradients in the handle, and waits for `stream`: a label outside {0, 1} is found on the
+ * device and returned as RS_ERR_ARG.  Checks before any device call, in this order: null pointers, B < 1, L < 1 or ld < L
+ * (RS_ERR_ARG); L >> n_layers < 1 (RS_ERR_LENGTH); ws_bytes (RS_ERR_WORKSPACE); B > rs_train_max_batch (RS_ERR_ARG).
+ * rs_train_evaluate: the forward pass and the head alone, same outputs, gradients untouched.
+ * rs_train_adam_step: one step on the gradients of the last rs_train_forward_backward (the step count lives in the handle;
+ * no weight decay, no amsgrad), then the packed weight forms the kernels read are rebuilt on the device.
+ * rs_train_get_params / set_params / get_grads: one tensor per call between the device and a host array in the reference's
+ * shape; index 2 l = layers.l.0.weight, 2 l + 1 = layers.l.0.bias, 2 n_layers = classifier.2.weight, 2 n_layers + 1 = its bias;
+ * count = the tensor's elements.
+ * rs_train_debug_copy (test hook): layer `layer`'s buffer as the last rs_train_forward_backward left it in ITS workspace,
+ * device to device - what 0: pooled rows fp32 [B][L >> (layer + 1)][cp4(c_out)], 1: selectors uint8 in the same shape (1:
+ * conv row 2 j + 1 won), 2: the gradient dY arriving at those pooled rows, fp32, same shape (cp4(c) = c rounded up to 4; pad
+ * channels are not written). */
+typedef struct rs_train rs_train;
+RS_API int rs_train_create(const rs_gconv_conv* convs, int n_layers, const float* fc_w /* [2, c_last] */, const float* fc_b,
+                           int device, rs_train** out);
+RS_API int rs_train_destroy(rs_train* h);
+RS_API size_t rs_train_workspace_bytes(const rs_train* h, int B, int L);
+RS_API int rs_train_max_batch(const rs_train* h, int L);
+RS_API int rs_train_slice_plan(const rs_train* h, int layer, int B, int L, int32_t* n_slices, int32_t* slice_len);
+RS_API int rs_train_forward_backward(rs_train* h, const float* d_x, const int32_t* d_labels, int B, int L, int ld, void* d_ws,
+                                     size_t ws_bytes, float* d_out /* [2 + 2 B] */, void* stream);
+RS_API int rs_train_evaluate(rs_train* h, const float* d_x, const int32_t* d_labels, int B, int L, int ld, void* d_ws,
+                             size_t ws_bytes, float* d_out /* [2 + 2 B] */, void* stream);
+RS_API int rs_train_adam_step(rs_train* h, float lr, float beta1, float beta2, float eps, void* stream);
+RS_API int rs_train_get_params(rs_train* h, int index, float* dst, size_t count);
+RS_API int rs_train_set_params(rs_train* h, int index, const float* src, size_t count);
+RS_API int rs_train_get_grads(rs_train* h, int index, float* dst, size_t count);
+RS_API int rs_train_debug_copy(rs_train* h, int layer, int what, void* d_dst, size_t bytes);
+
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag

@@ -33,6 +33,9 @@ SYMBOLS = (
     "rs_gconv_create", "rs_gconv_destroy", "rs_gconv_min_length", "rs_gconv_max_batch", "rs_gconv_workspace_bytes",
     "rs_gconv_forward_ragged", "rs_gconv_layer_plan", "rs_gconv_set_mode", "rs_gconv_x3_layout",
     "rs_polya_coords_workspace_bytes", "rs_polya_coords", "rs_retrain_prepare",
+    "rs_train_create", "rs_train_destroy", "rs_train_workspace_bytes", "rs_train_max_batch", "rs_train_slice_plan",
+    "rs_train_forward_backward", "rs_train_evaluate", "rs_train_adam_step", "rs_train_get_params", "rs_train_set_params",
+    "rs_train_get_grads", "rs_train_debug_copy",
 )
 
 
@@ -202,6 +205,26 @@ def lib():
     L.rs_polya_coords.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
     L.rs_retrain_prepare.restype = i32
     L.rs_retrain_prepare.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, vp, C.POINTER(vp), vp, vp]
+    L.rs_train_create.restype = i32
+    L.rs_train_create.argtypes = [vp, i32, vp, vp, i32, C.POINTER(vp)]
+    L.rs_train_destroy.restype = i32
+    L.rs_train_destroy.argtypes = [vp]
+    L.rs_train_workspace_bytes.restype = sz
+    L.rs_train_workspace_bytes.argtypes = [vp, i32, i32]
+    L.rs_train_max_batch.restype = i32
+    L.rs_train_max_batch.argtypes = [vp, i32]
+    L.rs_train_slice_plan.restype = i32
+    L.rs_train_slice_plan.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    for fn in (L.rs_train_forward_backward, L.rs_train_evaluate):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp, vp]
+    L.rs_train_adam_step.restype = i32
+    L.rs_train_adam_step.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, vp]
+    for fn in (L.rs_train_get_params, L.rs_train_set_params, L.rs_train_get_grads):
+        fn.restype = i32
+        fn.argtypes = [vp, i32, vp, sz]
+    L.rs_train_debug_copy.restype = i32
+    L.rs_train_debug_copy.argtypes = [vp, i32, i32, vp, sz]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32
