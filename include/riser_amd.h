@@ -646,10 +646,26 @@ RS_API int rs_retrain_prepare(const void* d_sig, int elem_bytes, const int64_t* 
  * rs_train_debug_copy (test hook): layer `layer`'s buffer as the last rs_train_forward_backward left it in ITS workspace,
  * device to device - what 0: pooled rows fp32 [B][L >> (layer + 1)][cp4(c_out)], 1: selectors uint8 in the same shape (1:
  * conv row 2 j + 1 won), 2: the gradient dY arriving at those pooled rows, fp32, same shape (cp4(c) = c rounded up to 4; pad
- * channels are not written). */
+ * channels are not written).
+ *
+ * rs_train_create_generic makes the same handle type for the net of the generic ConvNet family (rs_gconv_create): n_layers x
+ * [depth x (Conv1d(k_i, stride 1, 'same') + ReLU), MaxPool1d(2, 2)], `gap_fc`, any depth, every k_i odd.  convs is the table
+ * rs_gconv_create takes: n_layers * depth records, layer-major, conv j = layer * depth + d, weights [c_out][c_in][k].  It
+ * refuses, before a device is touched and with RS_ERR_ARG, exactly what rs_gconv_create refuses: an even kernel, channels that
+ * do not chain from 1, more than 16 layers, a depth outside 1-64, a conv that fits no tile shape of the inference family - a
+ * net that trains is a net that runs.  rs_train_create itself still takes kernels of 3 at depth 1 only.
+ * Every other rs_train_* call works on a handle from either constructor.  Where a call takes `layer` or a tensor index it
+ * means the CONV index j: tensors 2 j = layers.{j / depth}.{2 (j % depth)}.weight, 2 j + 1 = its bias, 2 n_convs and
+ * 2 n_convs + 1 the Linear - at depth 1 the numbering above.  rs_train_slice_plan(j) contracts B * (L >> (j / depth))
+ * positions.  The last conv of a layer pools and has the three buffers above with L >> (j / depth + 1) rows.  A conv that is
+ * not the last of its layer keeps every row: rs_train_debug_copy's what 0 is its ReLU rows and what 2 their gradient, both
+ * fp32 [B][L >> (j / depth)][cp4(c_out)], and what 1 is RS_ERR_ARG - it has no selectors; the backward pass gates on row > 0.
+ * The workspace holds those full-resolution rows and gradients too, and rs_train_max_batch applies the window to them. */
 typedef struct rs_train rs_train;
 RS_API int rs_train_create(const rs_gconv_conv* convs, int n_layers, const float* fc_w /* [2, c_last] */, const float* fc_b,
                            int device, rs_train** out);
+RS_API int rs_train_create_generic(const rs_gconv_conv* convs /* [n_layers * depth] */, int n_layers, int depth,
+                                   const float* fc_w /* [2, c_last] */, const float* fc_b, int device, rs_train** out);
 RS_API int rs_train_destroy(rs_train* h);
 RS_API size_t rs_train_workspace_bytes(const rs_train* h, int B, int L);
 RS_API int rs_train_max_batch(const rs_train* h, int L);

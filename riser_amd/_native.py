@@ -35,7 +35,7 @@ SYMBOLS = (
     "rs_polya_coords_workspace_bytes", "rs_polya_coords", "rs_retrain_prepare",
     "rs_train_create", "rs_train_destroy", "rs_train_workspace_bytes", "rs_train_max_batch", "rs_train_slice_plan",
     "rs_train_forward_backward", "rs_train_evaluate", "rs_train_adam_step", "rs_train_get_params", "rs_train_set_params",
-    "rs_train_get_grads", "rs_train_debug_copy",
+    "rs_train_get_grads", "rs_train_debug_copy", "rs_train_create_generic",
 )
 
 
@@ -207,6 +207,8 @@ def lib():
     L.rs_retrain_prepare.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, vp, C.POINTER(vp), vp, vp]
     L.rs_train_create.restype = i32
     L.rs_train_create.argtypes = [vp, i32, vp, vp, i32, C.POINTER(vp)]
+    L.rs_train_create_generic.restype = i32
+    L.rs_train_create_generic.argtypes = [vp, i32, i32, vp, vp, i32, C.POINTER(vp)]
     L.rs_train_destroy.restype = i32
     L.rs_train_destroy.argtypes = [vp]
     L.rs_train_workspace_bytes.restype = sz

@@ -1,5 +1,6 @@
-"""Train the shipped ConvNet class on the GPU (riser/train.py; riser/nets/cnn.py:12-18,43-65 at depth 1, every kernel 3,
-`gap_fc`, two classes): forward, cross-entropy, backward and Adam are the HIP kernels of csrc/train.hip (rs_train_*).
+"""Train the ConvNet on the GPU (riser/train.py; riser/nets/cnn.py:12-18,43-65 with `gap_fc`, two classes): forward,
+cross-entropy, backward and Adam are the HIP kernels of csrc/train.hip (rs_train_*).  `Trainer` is the shipped class (depth 1,
+every kernel 3), `GenericTrainer` any `depth` and any odd `kernels` - every net riser_amd.gconv runs; `trainer_for` picks.
 
     python -m riser_amd.train EXP_DIR DATA_DIR CHECKPT|None CONFIG.yaml START_EPOCH
 
@@ -54,6 +55,89 @@ def check_config(config) -> list:
     return channels[:n_layers]
 
 
+def check_generic_config(config):
+    """(channels, kernels, depth) of a config GenericTrainer trains - what the generic inference family (riser_amd.gconv)
+    runs: any depth >= 1, every kernel odd, `gap_fc`, two classes, fp32; ValueError - before any GPU call - for everything
+    else, a conv that fits no tile shape of that family included"""
+    from .gconv import layer_plan
+    model = getattr(config, "model", "cnn")
+    if model != "cnn":
+        raise ValueError(f"model {model!r}: riser_amd.train trains the `cnn` model only")
+    dtype = getattr(config, "dtype", "f32")
+    if dtype not in ("f32", "fp32", "float32"):
+        raise ValueError(f"dtype {dtype!r}: riser_amd.train is fp32 only")
+    cnn = config.cnn
+    n_layers, depth = int(cnn.n_layers), int(getattr(cnn, "depth", 1))
+    channels, kernels = [int(v) for v in cnn.channels], [int(v) for v in cnn.kernels]
+    if n_layers < 1 or n_layers > 16 or depth < 1 or depth > 64:
+        raise ValueError(f"n_layers {n_layers} / depth {depth}: riser_amd.train trains 1-16 layers of depth 1-64")
+    if len(channels) < n_layers or len(kernels) < n_layers:
+        raise ValueError(f"channels {channels} / kernels {kernels}: shorter than n_layers {n_layers}")
+    channels, kernels = channels[:n_layers], kernels[:n_layers]
+    if any(k < 1 or k % 2 == 0 for k in kernels):
+        raise ValueError(f"kernels {kernels}: even conv kernels ('same' pads them asymmetrically) are not supported")
+    if any(c < 1 for c in channels):
+        raise ValueError(f"channels {channels}: every layer needs at least one")
+    classifier = getattr(cnn, "classifier", "gap_fc")
+    if classifier != "gap_fc":
+        raise ValueError(f"classifier {classifier!r}: riser_amd.train trains the `gap_fc` head only")
+    if int(cnn.n_classes) != 2:
+        raise ValueError("riser_amd.train trains two-class heads only")
+    c_in = 1
+    for c, k in zip(channels, kernels):
+        for _ in range(depth):
+            try:
+                layer_plan(c_in, c, k)
+            except nv.NativeError as e:
+                raise ValueError(f"conv {c_in} -> {c}, kernel {k}: the generic ConvNet family could not run it ({e})") from None
+            c_in = c
+    return channels, kernels, depth
+
+
+def is_shipped_class(config) -> bool:
+    """True: check_config takes the config (Trainer's class); False: check_generic_config does; ValueError: neither"""
+    try:
+        check_config(config)
+        return True
+    except ValueError:
+        check_generic_config(config)
+        return False
+
+
+def generic_param_keys(n_layers: int, depth: int) -> list:
+    """the reference's state-dict keys in the order of the tensor index: conv j = layer * depth + d is layers.{layer}.{2 d}
+    (nn.Sequential of conv, ReLU, conv, ReLU, ..., MaxPool1d: riser/nets/cnn.py:52-65)"""
+    keys = []
+    for i in range(n_layers):
+        for d in range(depth):
+            keys += [f"layers.{i}.{2 * d}.weight", f"layers.{i}.{2 * d}.bias"]
+    return keys + ["classifier.2.weight", "classifier.2.bias"]
+
+
+def generic_param_shapes(channels, kernels, depth) -> dict:
+    shapes, c_in = {}, 1
+    for i, (c, k) in enumerate(zip(channels, kernels)):
+        for d in range(depth):
+            shapes[f"layers.{i}.{2 * d}.weight"], shapes[f"layers.{i}.{2 * d}.bias"] = (c, c_in, k), (c,)
+            c_in = c
+    shapes["classifier.2.weight"], shapes["classifier.2.bias"] = (2, c_in), (2,)
+    return shapes
+
+
+def generic_init_state(channels, kernels, depth) -> dict:
+    """torch's own initialisation of nn.Conv1d / nn.Linear tensors of the net's shapes, on the CPU, in the reference's
+    construction order"""
+    sd, c_in = {}, 1
+    for i, (c, k) in enumerate(zip(channels, kernels)):
+        for d in range(depth):
+            conv = torch.nn.Conv1d(c_in, c, k)
+            sd[f"layers.{i}.{2 * d}.weight"], sd[f"layers.{i}.{2 * d}.bias"] = conv.weight.detach(), conv.bias.detach()
+            c_in = c
+    fc = torch.nn.Linear(c_in, 2)
+    sd["classifier.2.weight"], sd["classifier.2.bias"] = fc.weight.detach(), fc.bias.detach()
+    return sd
+
+
 def param_keys(n_layers: int) -> list:
     """the reference's state-dict keys in the order of rs_train_get_params' tensor index"""
     keys = []
@@ -83,10 +167,10 @@ def init_state(channels) -> dict:
     return sd
 
 
-def _checked_state(state, channels) -> dict:
+def _checked_state(state, channels, shapes=None) -> dict:
     sd = load_state(state)
     out = {}
-    for key, shape in param_shapes(channels).items():
+    for key, shape in (shapes if shapes is not None else param_shapes(channels)).items():
         if key not in sd:
             raise ValueError(f"state dict has no {key!r}")
         a = np.ascontiguousarray(sd[key], dtype=np.float32)
@@ -199,7 +283,7 @@ class Trainer:
         return self._tensors("rs_train_get_params")
 
     def load_state_dict(self, state):
-        sd = _checked_state(state, self.channels)
+        sd = _checked_state(state, self.channels, self._shapes)
         for i, key in enumerate(self._keys):
             nv.check(nv.lib().rs_train_set_params(self._h, i, sd[key].ctypes.data, sd[key].size), "rs_train_set_params")
 
@@ -212,6 +296,67 @@ class Trainer:
         nv.check(nv.lib().rs_train_debug_copy(self._h, layer, {"y": 0, "sel": 1, "dy": 2}[what], dst.data_ptr(),
                                               dst.numel() * dst.element_size()), "rs_train_debug_copy")
         return dst[:, :, :c].cpu()
+
+
+class GenericTrainer(Trainer):
+    """Trainer's surface for any depth and any odd kernels (rs_train_create_generic).  Where a method takes `layer` it means
+    the conv index j = layer * depth + d, as the C ABI does."""
+
+    def __init__(self, config, state_dict=None, device=None, dtype: str = "f32"):
+        if dtype not in ("f32", "fp32", "float32"):
+            raise ValueError(f"dtype {dtype!r}: riser_amd.train is fp32 only")
+        self._h = None
+        self._ws = None
+        self.channels, self.kernels, self.depth = check_generic_config(config)
+        self.learning_rate = float(getattr(config, "learning_rate", 1e-3))
+        self.n_layers = len(self.channels)
+        self._keys = generic_param_keys(self.n_layers, self.depth)
+        self._shapes = generic_param_shapes(self.channels, self.kernels, self.depth)
+        keep = _checked_state(state_dict if state_dict is not None
+                              else generic_init_state(self.channels, self.kernels, self.depth), self.channels, self._shapes)
+        nv.require_gpu()
+        d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
+        self._h = create_generic_handle(self.channels, self.kernels, self.depth, keep, self.device.index)
+
+    def state_dict(self) -> dict:
+        """the reference's keys as CPU fp32 tensors (riser/nets/cnn.py's state dict at this depth with `gap_fc`)"""
+        return self._tensors("rs_train_get_params")
+
+    def debug_copy(self, layer: int, what: str, B: int, L: int) -> torch.Tensor:
+        """conv `layer`'s 'y' (the last conv of a layer: pooled rows; an inner conv: its ReLU rows), 'sel' (selectors, pooling
+        convs only) or 'dy' (the gradient arriving at 'y') of the last forward + backward of B reads of L samples, on the host"""
+        level, pools = layer // self.depth, layer % self.depth == self.depth - 1
+        c = self.channels[level]
+        cp, rows = (c + 3) & ~3, (L >> level) >> (1 if pools else 0)
+        dst = torch.empty((B, rows, cp), dtype=torch.uint8 if what == "sel" else torch.float32, device=self.device)
+        nv.check(nv.lib().rs_train_debug_copy(self._h, layer, {"y": 0, "sel": 1, "dy": 2}[what], dst.data_ptr(),
+                                              dst.numel() * dst.element_size()), "rs_train_debug_copy")
+        return dst[:, :, :c].cpu()
+
+
+def trainer_for(config, state_dict=None, device=None):
+    """a Trainer for the shipped class (depth 1, every kernel 3), a GenericTrainer for every other net check_generic_config
+    accepts; ValueError before any GPU call for the rest"""
+    if is_shipped_class(config):
+        return Trainer(config, state_dict, device)
+    return GenericTrainer(config, state_dict, device)
+
+
+def create_generic_handle(channels, kernels, depth, state, device_index: int):
+    """rs_train_create_generic on the arrays of `state` ({reference key: float32 array}); device_index < 0 as create_handle"""
+    convs = (_Conv * (len(channels) * depth))()
+    c_in = 1
+    for i, (c, k) in enumerate(zip(channels, kernels)):
+        for d in range(depth):
+            convs[i * depth + d] = _Conv(c_in, c, k, 0, state[f"layers.{i}.{2 * d}.weight"].ctypes.data,
+                                         state[f"layers.{i}.{2 * d}.bias"].ctypes.data)
+            c_in = c
+    h = C.c_void_p()
+    nv.check(nv.lib().rs_train_create_generic(convs, len(channels), int(depth), state["classifier.2.weight"].ctypes.data,
+                                              state["classifier.2.bias"].ctypes.data, int(device_index), C.byref(h)),
+             "rs_train_create_generic")
+    return h
 
 
 def create_handle(channels, state, device_index: int):
@@ -357,11 +502,11 @@ def main(argv=None) -> int:
     a = parse_args(argv)
     print(f"Experiment dir: {a.exp_dir}\nData dir: {a.data_dir}\nCheckpoint: {a.checkpt}\nConfig file: {a.config_file}")
     config = get_config(a.config_file)
-    check_config(config)
+    is_shipped_class(config)
     print("Creating data loaders...")
     sets = {split: {k: load_set(os.path.join(a.data_dir, k, split)) for k in LENGTH_KEYS} for split in ("train", "val")}
     state = os.path.join(a.exp_dir, a.checkpt) if a.checkpt is not None else None
-    trainer = Trainer(config, state)
+    trainer = trainer_for(config, state)
     try:
         fit(trainer, sets["train"], sets["val"], int(config.n_epochs), int(config.batch_size), a.exp_dir, a.exp_id, a.start_epoch)
     finally:

@@ -3,7 +3,11 @@
 HIP kernels against the same net written in PyTorch and run eagerly on the same GPU in the same process.
 
     python tools/train_bench.py [--steps 20] [--rounds 3] [--lengths 8000,12000,16000] [--batch 32]
+    python tools/train_bench.py --depth 2 --kernels 5 [--lengths 16000]
     python tools/train_bench.py --kernels [--lengths 16000]
+
+--depth and --kernels K (one odd width for every layer, or a comma list of twelve) time a generic net on the shipped channel
+list instead - riser_amd.train.GenericTrainer, torch's own initialisation under a fixed seed.
 
 Step times come from device events around `--steps` steps after a warm-up of every shape; the two implementations are
 interleaved round by round, and the median round is reported with the spread.  --kernels runs this family's steps alone in
@@ -28,18 +32,30 @@ import torch  # noqa: E402
 from riser_amd import synth  # noqa: E402
 
 
-def config():
-    return types.SimpleNamespace(model="cnn", learning_rate=1e-3, cnn=synth.CnnConfig())
+def config(kernels=None, depth=1):
+    cnn = synth.CnnConfig(kernels=kernels or synth.KERNELS, depth=depth)
+    return types.SimpleNamespace(model="cnn", learning_rate=1e-3, cnn=cnn)
 
 
-def torch_net(state, dev):
+def state_of(cfg):
+    """the synthetic shipped state dict, or - for a generic net - torch's own initialisation under a fixed seed"""
+    from riser_amd import train as T
+    if T.is_shipped_class(cfg):
+        return {k: torch.from_numpy(v) for k, v in synth.make_state_dict(1).items()}
+    torch.manual_seed(1)
+    return T.generic_init_state(*T.check_generic_config(cfg))
+
+
+def torch_net(state, dev, cfg):
     layers, c_in = [], 1
-    for i, c in enumerate(synth.CHANNELS):
-        conv = torch.nn.Conv1d(c_in, c, 3, padding="same")
-        conv.weight.data.copy_(state[f"layers.{i}.0.weight"])
-        conv.bias.data.copy_(state[f"layers.{i}.0.bias"])
-        layers += [conv, torch.nn.ReLU(inplace=True), torch.nn.MaxPool1d(2, 2)]
-        c_in = c
+    for i, (c, k) in enumerate(zip(cfg.cnn.channels, cfg.cnn.kernels)):
+        for d in range(cfg.cnn.depth):
+            conv = torch.nn.Conv1d(c_in, c, k, padding="same")
+            conv.weight.data.copy_(state[f"layers.{i}.{2 * d}.weight"])
+            conv.bias.data.copy_(state[f"layers.{i}.{2 * d}.bias"])
+            layers += [conv, torch.nn.ReLU(inplace=True)]
+            c_in = c
+        layers.append(torch.nn.MaxPool1d(2, 2))
     fc = torch.nn.Linear(c_in, 2)
     fc.weight.data.copy_(state["classifier.2.weight"])
     fc.bias.data.copy_(state["classifier.2.bias"])
@@ -61,10 +77,10 @@ def data(B, L, dev):
     return torch.randn((B, L), generator=g).to(dev), torch.randint(0, 2, (B,), generator=g).to(dev)
 
 
-def steps_only(lengths, B, steps):
-    from riser_amd.train import Trainer
+def steps_only(lengths, B, steps, cfg):
+    from riser_amd.train import trainer_for
     dev = torch.device("cuda", 0)
-    t = Trainer(config(), {k: torch.from_numpy(v) for k, v in synth.make_state_dict(1).items()}, device=dev)
+    t = trainer_for(cfg, state_of(cfg), device=dev)
     for L in lengths:
         x, y = data(B, L, dev)
         for _ in range(steps):
@@ -73,11 +89,11 @@ def steps_only(lengths, B, steps):
     t.close()
 
 
-def kernels(lengths, B, steps):
+def kernels(lengths, B, steps, net_args):
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable,
                os.path.abspath(__file__), "--steps-only", "--steps", str(steps), "--batch", str(B),
-               "--lengths", ",".join(str(v) for v in lengths)]
+               "--lengths", ",".join(str(v) for v in lengths), *net_args]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             sys.exit("rocprofv3 failed:\n" + r.stderr[-2000:])
@@ -102,23 +118,35 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--lengths", type=lambda s: [int(v) for v in s.split(",")], default=[8000, 12000, 16000])
-    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--depth", type=int, default=1, help="convs per layer (default 1)")
+    ap.add_argument("--kernels", nargs="?", const="profile", default=None, metavar="K[,K...]",
+                    help="with a value: the conv kernel width(s) of the net; without: per-kernel times under rocprofv3")
+    ap.add_argument("--profile", action="store_true", help="per-kernel times under rocprofv3 (what a bare --kernels asks for)")
     ap.add_argument("--steps-only", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    if a.kernels:
-        return kernels(a.lengths, a.batch, min(a.steps, 5))
+    widths = None
+    if a.kernels == "profile":
+        a.profile = True
+    elif a.kernels is not None:
+        widths = [int(v) for v in a.kernels.split(",")]
+        widths = widths * len(synth.CHANNELS) if len(widths) == 1 else widths
+    cfg = config(widths, a.depth)
+    net_args = ["--depth", str(a.depth)] + (["--kernels", a.kernels] if widths else [])
+    if a.profile:
+        return kernels(a.lengths, a.batch, min(a.steps, 5), net_args)
     if a.steps_only:
-        return steps_only(a.lengths, a.batch, a.steps)
-    from riser_amd.train import Trainer
+        return steps_only(a.lengths, a.batch, a.steps, cfg)
+    from riser_amd.train import trainer_for
     assert torch.cuda.is_available(), "train_bench.py needs an MI355X"
     dev = torch.device("cuda", 0)
-    state = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(1).items()}
-    ours = Trainer(config(), state, device=dev)
-    net = torch_net(state, dev)
+    state = state_of(cfg)
+    ours = trainer_for(cfg, state, device=dev)
+    net = torch_net(state, dev, cfg)
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     loss_fn = torch.nn.CrossEntropyLoss()
-    print(f"{torch.cuda.get_device_name(0)}; batch {a.batch}; {a.steps} steps per window, {a.rounds} interleaved rounds; "
-          "ms per step (forward + backward + Adam), median [min .. max]")
+    print(f"{torch.cuda.get_device_name(0)}; {type(ours).__name__}, {len(cfg.cnn.channels)} layers, depth {cfg.cnn.depth}, "
+          f"kernels {sorted(set(cfg.cnn.kernels[:cfg.cnn.n_layers]))}; batch {a.batch}; {a.steps} steps per window, "
+          f"{a.rounds} interleaved rounds; ms per step (forward + backward + Adam), median [min .. max]")
     for L in a.lengths:
         x, y = data(a.batch, L, dev)
 
