@@ -86,7 +86,7 @@ struct Hooks {
     bool h16_wres = true;            // RS_H16_WRES=0: narrow 16-bit layers on the ring kernel instead of the weights-resident one
     int wres_f32 = -1;               // RS_WRES_F32: 0 = never the fp32 weights-resident kernel (conv_wres_f32.hip), 1 = on every eligible layer
                                      // whatever the launch size (tests, A/B; default -1: on launches that give every wave a run of steps)
-    char plan_kc[128] = "";          // RS_PLAN_KC "layer:kc;...": forces the channel chunk of an F(4,3) layer (convnet_model.hpp: plan_static_wino4)
+    char plan_kc[128] = "";          // RS_PLAN_KC "layer:kc;...": forces the channel chunk of an F(4,3) layer, "layer:20u" with the unpadded tiles (convnet_model.hpp: plan_static_wino4)
     char x3_terms[128] = "";         // RS_X3_TERMS "layer:mask;...": -DRS_X3_MASK measurement builds only (ConvLayerDev::x3_terms)
     bool wino4_set = false;          // RS_WINO4: comma list of the layers that run F(4,3) ("none": F(2,3) everywhere), instead of
     char wino4[128] = "";            // the rule of convnet_model.hpp: use_wino4
@@ -165,6 +165,7 @@ struct ConvPlan {
     int kc;           // input channels per K chunk (fp32: multiple of 4; 16-bit: 32 = one MFMA k-step)
     int nch;          // number of chunks: kc * nch >= cp_in
     int n_alloc;      // rows of the packed weight / bias tables (couts + zero rows for any tile width)
+    bool unpadded;    // F(4,3): the layer may run the tiles that fit the LDS on unpadded rows only (conv_wino_device.hpp: wino_unpadded)
 };
 
 struct ConvLayerDev {
@@ -203,8 +204,8 @@ int launch_conv_wino(const ConvLayerDev& L, const float* d_x, float* d_y, const 
 int launch_conv_wino4(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len, int B, int P_in,
                       int layer_index, int num_cu, int check_dead, hipStream_t st, int* bm_out, int* bn_out);
 int conv_wino4_max_bn();
-double conv_wino4_plan_cost(int64_t groups, int n16, int kc, int nch, int num_cu);
-double conv_wino4_launch_cost(int64_t groups, int n16, int kc, int nch, int num_cu, bool* thin_out);
+double conv_wino4_plan_cost(int64_t groups, int n16, int kc, int nch, bool unpadded, int num_cu);
+double conv_wino4_launch_cost(int64_t groups, int n16, int kc, int nch, bool unpadded, int num_cu, bool* thin_out);
 bool conv_wino_can_fuse0(const ConvLayerDev& L, int P_in);
 // fp32 Winograd, layers 0 + 1 of the shipped net as one LDS-free streaming kernel (conv_stream_f32.hip)
 bool conv_stream_f32_ok(const ConvLayerDev& L1, int c0, int P_in1);

@@ -22,8 +22,13 @@
 // those of conv_wino.hip; what differs: the input slab is split into FOUR planes by (row mod 4) so that the
 // six inputs of group G are rows G, G+1 of the planes (unit lane stride, pitch KC + 2: conflict-free
 // ds_read_b32), the weight slab has six components, a slot = (k-step, component) carries MT * NT MFMAs
-// with MT * NT <= 5 (6 x 4 accumulator registers per 16 x 16 sub-tile), and LDS capacity limits the channel
-// chunk to 16 or 20.  Used for the layers where the matrix pipe is the bound (chosen in rs_model_create).
+// with MT * NT <= 6 (6 x 4 accumulator registers per 16 x 16 sub-tile), and LDS capacity limits the channel
+// chunk: 16 or 20, and at 20 the tile.  512 x 64 holds chunks of 20 at the pitch of 22 floats; 512 x 80 would need
+// 175 296 B and runs them on UNPADDED rows (159 360 B) with the k index swizzled by bit 3 of the row, which keeps
+// every fragment read on 32 banks (conv_wino_device.hpp: wino_unpadded, wino_swizzle; tests/wino_lds_check.cpp);
+// 512 x 96 (174 720 B even so) runs chunks of 16 only.  A layer of 100 padded channels is 5 chunks of 20 instead of
+// 7 of 16 (112 K steps, 12 of them zeros); the MFMA order per accumulator is channels ascending whatever the chunk, so
+// the bits do not depend on it.  Used for the layers where the matrix pipe is the bound (chosen in rs_model_create).
 #include "conv_wino_host.hpp"
 
 #include <stdio.h>
@@ -108,6 +113,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
     const bool b_act = b_n < NPP;
     const int a_st = (a_row & 3) * PL + (a_row >> 2) * S + 4 * a_c4;                     // + u * (RPT/4) * S
     const int b_st = A_ELEMS + ((b_rem / KQ) * BN + b_n) * S + 4 * (b_rem % KQ);         // + u * NPP * S
+    const int a_h0 = (a_row >> 5) & 1, b_h0 = (b_n >> 3) & 1;      // swizzled rows: bit 3 of the thread's first plane index / of its n
     const unsigned a_tb = (unsigned)(a_row * a.cp_in + 4 * a_c4) * 4u;
     const unsigned b_tb = (unsigned)(b_n * a.nch * NC * KCT + 4 * b_rem) * 4u;
     const unsigned a_step = (unsigned)(RPT * a.cp_in) * 4u;
@@ -152,8 +158,15 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
 #endif
             if (act) {
                 uint2* d = reinterpret_cast<uint2*>(buf + a_st + u * (RPT / 4) * S);
-                d[0] = make_uint2(ra[u].x, ra[u].y);
-                d[1] = make_uint2(ra[u].z, ra[u].w);
+                if constexpr (T::SWZ) {                // the halves change places in the rows with bit 3 set
+                    int h = (((a_row >> 2) + u * (RPT / 4)) >> 3) & 1;
+                    if constexpr (RPT % 32 == 0) h = a_h0 ^ ((u * (RPT / 32)) & 1);   // the same, without arithmetic per unit
+                    d[h] = make_uint2(ra[u].x, ra[u].y);
+                    d[h ^ 1] = make_uint2(ra[u].z, ra[u].w);
+                } else {
+                    d[0] = make_uint2(ra[u].x, ra[u].y);
+                    d[1] = make_uint2(ra[u].z, ra[u].w);
+                }
             }
         } else {
             constexpr int v = u - A_PER;
@@ -165,8 +178,15 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
 #endif
             if (act) {
                 uint2* d = reinterpret_cast<uint2*>(buf + b_st + v * NPP * S);
-                d[0] = make_uint2(rb[v].x, rb[v].y);
-                d[1] = make_uint2(rb[v].z, rb[v].w);
+                if constexpr (T::SWZ) {                // row = component * BN + n: bit 3 is n's
+                    int h = ((b_n + v * NPP) >> 3) & 1;
+                    if constexpr (NPP % 16 == 0) h = b_h0;
+                    d[h] = make_uint2(rb[v].x, rb[v].y);
+                    d[h ^ 1] = make_uint2(rb[v].z, rb[v].w);
+                } else {
+                    d[0] = make_uint2(rb[v].x, rb[v].y);
+                    d[1] = make_uint2(rb[v].z, rb[v].w);
+                }
             }
         }
     };
@@ -234,8 +254,12 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
     __syncthreads();
     int buf = 0;
 
-    const int a_rd = (wm * 16 * MT + r) * S + kq;                  // + (k & 3) * PL + (i * 16 + (k >> 2)) * S + c0
-    const int b_rd = A_ELEMS + (wn * 16 * NT + r) * S + kq;        // + (comp * BN + j * 16) * S + c0
+    // unpadded rows (512 x 80 at chunks of 20): the k lane is swizzled by bit 3 of the row it reads (wino_swizzle).  Raw input
+    // d_k of a lane's group is row r + (k >> 2) (+ multiples of 16), so d4 and d5 go by bit 3 of r + 1: two lane constants for
+    // the input fragments, one for the weights'; the k offsets of the slots are multiples of 4 and pass through the XOR
+    const int a_rd = (wm * 16 * MT + r) * S + (kq ^ T::swz(r));          // + (k & 3) * PL + (i * 16 + (k >> 2)) * S + c0
+    const int a_rd1 = (wm * 16 * MT + r) * S + (kq ^ T::swz(r + 1));     // the same for k = 4, 5
+    const int b_rd = A_ELEMS + (wn * 16 * NT + r) * S + (kq ^ T::swz(r));   // + (comp * BN + j * 16) * S + c0
 
     while (true) {
         int nc = c + 1, no = o;
@@ -252,6 +276,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
         if constexpr (!DEEP)
             if (has_next && nc == 0) tile_origin(no, nm0, nn0);
         const float* Ab = lds + buf * BUF + a_rd;
+        const float* Ab1 = T::SWZ ? lds + buf * BUF + a_rd1 : Ab;
         const float* Bb = lds + buf * BUF + b_rd;
         float* nbuf = lds + (buf ^ 1) * BUF;
         if constexpr (DEEP)
@@ -275,7 +300,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int k = 0; k < 6; ++k) dr[i][k] = Ab[(k & 3) * PL + (i * 16 + (k >> 2)) * S];
+            for (int k = 0; k < 6; ++k) dr[i][k] = (k < 4 ? Ab : Ab1)[(k & 3) * PL + (i * 16 + (k >> 2)) * S];
         static_for<AH>([&](auto SL) {
             constexpr int sl = decltype(SL)::value;
 #pragma unroll
@@ -304,7 +329,7 @@ __global__ __launch_bounds__(512) void conv_wino4_kernel(const Wino4Args a) {   
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
-                    for (int k = 0; k < 6; ++k) RS_FRAG_A(dr[i][k], Ab[(k & 3) * PL + (i * 16 + (k >> 2)) * S + c0]);
+                    for (int k = 0; k < 6; ++k) RS_FRAG_A(dr[i][k], (k < 4 ? Ab : Ab1)[(k & 3) * PL + (i * 16 + (k >> 2)) * S + c0]);
             }
             if constexpr (xf_next) wino_input_transform<4>(v[(st + 1) & 1][comp - XF0], dr[comp - XF0]);
             if constexpr (sl + AH < NSLOTS) {
@@ -436,6 +461,7 @@ using Shape = WinoShape<Wino4Args, 2>;     // chunk = 16, 20
 #define RS_SHAPE_4(WM, WN, MT, NT) \
     {{WM, WN, MT, NT}, {conv_wino4_kernel<WM, WN, MT, NT, 16, true>, conv_wino4_kernel<WM, WN, MT, NT, 20, true>}, {nullptr, nullptr}}
 const Shape kShapes[] = {
+    // 512 x 80 at chunks of 20: 223 registers, no scratch, unpadded LDS rows (above); layers 5, 6 and 10 of the shipped net take it.
     // 512 x 96 (round 6): 36 accumulator tiles = 249 / 253 registers, no scratch; its LDS fits with chunks of 16 only (157 KB), so
     // rs_model_create's chunk choice moves layers 7 and 9 of the shipped net (22 and 48 column groups: 4 and 8 tiles of six) from
     // chunks of 20 to 16 for it: layer 9 becomes ONE round of 256 tiles at 512 reads (-9 %), the fp32 step -1.3 %
@@ -459,23 +485,24 @@ constexpr int kNumShapes = sizeof(kShapes) / sizeof(kShapes[0]);
 constexpr WinoCost kCost = {6.0, 12.0, 0.02, 90.0, 23500.0, 71.6, 4.25, -920.0, 0.0062, 0.0124, -467.0, 554.0};
 
 // row unit: GROUPS of four conv rows
-auto family(int kc, int nch) { return wino_family<4>(kShapes, kNumShapes, kCost, kc, nch); }
+auto family(int kc, int nch, bool unpadded) { return wino_family<4>(kShapes, kNumShapes, kCost, kc, nch, unpadded); }
 
 }  // namespace
 
 int conv_wino4_max_bn() { return 256; }
 int conv_wino4_num_shapes() { return kNumShapes; }
 bool conv_wino4_shape_ok(const ConvLayerDev& L, int k) {
-    return k >= 0 && k < kNumShapes && wino_chunk_index<Shape>(L.plan.kc) >= 0 && family(L.plan.kc, L.plan.nch).can_run(k);
+    return k >= 0 && k < kNumShapes && wino_chunk_index<Shape>(L.plan.kc) >= 0 &&
+           family(L.plan.kc, L.plan.nch, L.plan.unpadded).can_run(k);
 }
 
 // planner's estimate (SIMD cycles) of one launch with the best tile shape for this chunk size: lets
 // rs_model_create pick the channel chunk (which fixes the weight packing) with the tile shapes it enables in mind
-double conv_wino4_plan_cost(int64_t groups, int n16, int kc, int nch, int num_cu) {
-    return choose_tile(family(kc, nch), groups, n16, num_cu, false).cost;
+double conv_wino4_plan_cost(int64_t groups, int n16, int kc, int nch, bool unpadded, int num_cu) {
+    return choose_tile(family(kc, nch, unpadded), groups, n16, num_cu, false).cost;
 }
-double conv_wino4_launch_cost(int64_t groups, int n16, int kc, int nch, int num_cu, bool* thin_out) {
-    return wino_launch_cost(family(kc, nch), groups, n16, num_cu, kCost, thin_out);
+double conv_wino4_launch_cost(int64_t groups, int n16, int kc, int nch, bool unpadded, int num_cu, bool* thin_out) {
+    return wino_launch_cost(family(kc, nch, unpadded), groups, n16, num_cu, kCost, thin_out);
 }
 
 int launch_conv_wino4(const ConvLayerDev& L, const float* d_x, float* d_y, const int32_t* d_len, int B, int P_in,

@@ -103,13 +103,16 @@ double wino_thin_tile_cost(const TileGeom& s, int kc, int nch, int per_cu, doubl
 }
 
 // the family as plan_tiles sees it (tile_plan.hpp), for a layer of nch chunks of kc channels.  A forced or tuned shape need
-// only fit the LDS: the four-wave entries, which no full-launch search picks, can be pinned.
+// only fit the LDS: the four-wave entries, which no full-launch search picks, can be pinned.  unpadded (ConvPlan): whether the
+// layer takes the tiles that fit on unpadded rows only; without it they are out of reach like the ones that do not fit.
 template <int M, class Shape>
-auto wino_family(const Shape* shapes, int n_shapes, const WinoCost& k, int kc, int nch) {
+auto wino_family(const Shape* shapes, int n_shapes, const WinoCost& k, int kc, int nch, bool unpadded = false) {
+    auto open = [=](int i) { return unpadded || !wino_unpadded(M, shapes[i].bm(), shapes[i].bn(), kc); };
     return tile_family(
-        n_shapes, [=](int i) -> const TileGeom& { return shapes[i]; }, [=](int i) { return wino_tile_cost<M>(shapes[i], kc, nch, k); },
-        [=](int i, int per_cu, double fill) { return wino_thin_tile_cost<M>(shapes[i], kc, nch, per_cu, fill, k); },
-        [=](int i) { return wino_lds_bytes<M>(shapes[i], kc) <= kConvLdsBudget; });
+        n_shapes, [=](int i) -> const TileGeom& { return shapes[i]; },
+        [=](int i) { return open(i) ? wino_tile_cost<M>(shapes[i], kc, nch, k) : -1.0; },
+        [=](int i, int per_cu, double fill) { return open(i) ? wino_thin_tile_cost<M>(shapes[i], kc, nch, per_cu, fill, k) : -1.0; },
+        [=](int i) { return open(i) && wino_lds_bytes<M>(shapes[i], kc) <= kConvLdsBudget; });
 }
 
 // index of channel chunk kc in a shape's instantiations (16, 20, ...), or -1
@@ -159,7 +162,7 @@ int launch_wino(const char* name, const Shape* shapes, int n_shapes, const WinoC
     }
     const int n16 = round_up(L.c_out, 16) / 16;
     const int64_t units = M == 2 ? rows64 / 2 : (rows64 + 3) / 4;
-    const TilePlan plan = plan_tiles(wino_family<M>(shapes, n_shapes, cost, p.kc, p.nch), units, n16, num_cu,
+    const TilePlan plan = plan_tiles(wino_family<M>(shapes, n_shapes, cost, p.kc, p.nch, p.unpadded), units, n16, num_cu,
                                      {force, layer_index, tuned_pick(L.force_shape, L.tuned, rows64), fused ? fuse.geom : nullptr},
                                      {!L.hooks->no_tail_split, L.hooks->tail_margin > 0 ? L.hooks->tail_margin : 0.97, true});
     if (!plan.n_parts) {

@@ -120,7 +120,7 @@ Kernel select_kernel(const rs_model* m, int i, int NB, int P_in, const Fuse0& fu
         const int n16 = round_up(L.c_out, 16) / 16;
         bool thin_fit = false;                               // the tiled estimate is the thin-launch fit (with its launch cost: like the small kernel's)
         const double cost = L.wino_m == 4
-            ? conv_wino4_launch_cost((rows_in + 3) / 4, n16, L.plan.kc, L.plan.nch, m->num_cu, &thin_fit)
+            ? conv_wino4_launch_cost((rows_in + 3) / 4, n16, L.plan.kc, L.plan.nch, L.plan.unpadded, m->num_cu, &thin_fit)
             : conv_wino_launch_cost(rows_in / 2, n16, L.plan.kc, L.plan.nch, m->num_cu, &thin_fit);
         const bool small32 = conv_small_f32_waves(L, rows_in) <= 4096 &&
                              conv_small_f32_cost(L, rows_in, m->num_cu) < (thin_fit ? 1.0 : 0.8) * cost;

@@ -118,23 +118,34 @@ ConvPlan plan_static_wino(int cp_in, int c_out) {
 
 // F(4,3): chunks of 16 or 20 channels (LDS capacity); 6 * kc / 4 slots per chunk
 // The chunk (16 or 20 channels; LDS capacity) fixes the weight packing, but also which tile shapes fit in LDS
-// (80-channel-wide tiles need chunks of 16), so it is chosen with the launch planner's own cost estimate at a
+// (96-channel-wide tiles need chunks of 16), so it is chosen with the launch planner's own cost estimate at a
 // nominal batch (512 reads of 16000 samples, BASELINE config 2).
-// tuning aid: RS_PLAN_KC = "layer:kc;layer:kc" forces the channel chunk of a layer when the model is created
+// Chunks of 20 come with the tiles that fit the LDS on unpadded rows only (512 x 80; ConvPlan::unpadded), which is what makes
+// them the cheaper chunk for 80-column layers.
+// tuning aid: RS_PLAN_KC = "layer:kc;layer:kc" forces the channel chunk of a layer when the model is created.  "layer:20" means
+// what it always has, the tiles at the row pitch of kc + 2 (the set tools/shape_sweep.py and the shape sweep of the tests walk,
+// by that footprint); "layer:20u" is the chunk as the planner takes it, unpadded tiles included.
 ConvPlan plan_static_wino4(const Hooks& h, int cp_in, int c_out, int layer, int num_cu) {
     ConvPlan p{};
     double best_cost = -1;
     const int64_t groups = (int64_t)512 * (16384 >> layer) / 4;
     int forced_kc = 0;
-    next_layer_value(h.plan_kc, layer, &forced_kc);                          // the layer's first entry, if it has one
+    bool forced_unpadded = false;
+    if (const char* end = next_layer_value(h.plan_kc, layer, &forced_kc)) {  // the layer's first entry, if it has one
+        const char* q = end;                                                 // its last character: before the ';' or the end
+        while (q > h.plan_kc && (q[-1] == ';' || q[-1] == ' ')) --q;
+        forced_unpadded = q > h.plan_kc && q[-1] == 'u';
+    }
     for (int kc = 16; kc <= 20; kc += 4) {
         if (forced_kc && kc != forced_kc) continue;
+        const bool unpadded = kc == 20 && (!forced_kc || forced_unpadded);
         const int nch = (cp_in + kc - 1) / kc;
-        const double cost = conv_wino4_plan_cost(groups, round_up(c_out, 16) / 16, kc, nch, num_cu);
+        const double cost = conv_wino4_plan_cost(groups, round_up(c_out, 16) / 16, kc, nch, unpadded, num_cu);
         if (best_cost < 0 || cost < best_cost) {
             best_cost = cost;
             p.kc = kc;
             p.nch = nch;
+            p.unpadded = unpadded;
         }
     }
     p.n_alloc = round_up(c_out, 16) + conv_wino4_max_bn();
