@@ -630,9 +630,11 @@ RS_API int rs_retrain_prepare(const void* d_sig, int elem_bytes, const int64_t* 
  * rs_train_workspace_bytes: the bytes one call of B reads of L samples needs - per layer the pooled rows, their gradient and
  * one selector byte per pooled element, the head's buffers, and the partial tiles of the sliced weight gradients; 0 for a
  * null handle or an L that leaves no row behind the last pool.  rs_train_max_batch: the largest B whose every buffer stays
- * inside the 2 GiB window.  rs_train_slice_plan: into how many slices of how many positions layer `layer`'s weight-gradient
- * contraction over B * (L >> layer) positions is cut - a function of (B, L, layer shape) alone, so the sums are the same
- * bits on every device and run.
+ * inside the 2 GiB window, and at most 65535 - the y extent of a launch grid, which holds the reads of the head's backward
+ * launch: every B it returns is a B every launch of a training call can express.  rs_train_slice_plan: into how many slices
+ * of how many positions layer `layer`'s weight-gradient contraction over B * (L >> layer) positions is cut - a function of
+ * (B, L, layer shape) alone, so the sums are the same bits on every device and run; at most 65535 slices, for the same
+ * reason.
  * rs_train_forward_backward writes d_out[0] = loss, d_out[1] = reads whose argmax equals their label, d_out[2 + 2 b + j] =
  * logit j of read b, leaves the gradients in the handle, and waits for `stream`: a label outside {0, 1} is found on the
  * device and returned as RS_ERR_ARG.  Checks before any device call, in this order: null pointers, B < 1, L < 1 or ld < L
@@ -644,7 +646,10 @@ RS_API int rs_retrain_prepare(const void* d_sig, int elem_bytes, const int64_t* 
  * shape; index 2 l = layers.l.0.weight, 2 l + 1 = layers.l.0.bias, 2 n_layers = classifier.2.weight, 2 n_layers + 1 = its bias;
  * count = the tensor's elements.
  * rs_train_debug_copy (test hook): layer `layer`'s buffer as the last rs_train_forward_backward left it in ITS workspace,
- * device to device - what 0: pooled rows fp32 [B][L >> (layer + 1)][cp4(c_out)], 1: selectors uint8 in the same shape (1:
+ * which the caller has kept alive and untouched since.  Every training call forgets that workspace when it begins and only
+ * an rs_train_forward_backward that returns RS_OK records its own: after an rs_train_evaluate - which carves the same
+ * workspace at the offsets of its own (B, L) - or after a refused call, rs_train_debug_copy is RS_ERR_ARG, never a mixture
+ * of two calls.  Device to device - what 0: pooled rows fp32 [B][L >> (layer + 1)][cp4(c_out)], 1: selectors uint8 in the same shape (1:
  * conv row 2 j + 1 won), 2: the gradient dY arriving at those pooled rows, fp32, same shape (cp4(c) = c rounded up to 4; pad
  * channels are not written).
  *

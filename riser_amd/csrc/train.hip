@@ -500,7 +500,8 @@ struct rs_train {
     size_t n_params = 0, fcw_off = 0, fcb_off = 0, n_packed = 0;
     rs::DevBuf<float> params, grads, m, v, packed;
     int64_t step = 0;
-    void* last_ws = nullptr;    // rs_train_debug_copy: the workspace, batch and length of the last rs_train_forward_backward
+    void* last_ws = nullptr;    // rs_train_debug_copy: the workspace, batch and length of the last rs_train_forward_backward,
+                                // null again once any later training call - an evaluate, a refused one - has begun
     int last_B = 0, last_L = 0;
 };
 
@@ -588,6 +589,7 @@ int check_train_call(const char* fn, const rs_train* h, const void* d_x, const v
 
 int run(rs_train* h, const char* fn, const float* d_x, const int32_t* d_labels, int B, int L, int ld, void* d_ws,
         size_t ws_bytes, float* d_out, void* stream, bool backward) {
+    if (h) h->last_ws = nullptr;                            // this call may carve the same workspace at other offsets
     const int rc = check_train_call(fn, h, d_x, d_labels, d_ws, d_out, B, L, ld, ws_bytes);
     if (rc != RS_OK) return rc;
     DeviceGuard guard(h->device);
@@ -676,9 +678,6 @@ int run(rs_train* h, const char* fn, const float* d_x, const int32_t* d_labels, 
             launch_conv<DGRAD>(a, s.pool, B, st);
             RS_HIP(hipGetLastError());
         }
-        h->last_ws = d_ws;
-        h->last_B = B;
-        h->last_L = L;
     }
     int32_t bad = 0;                                        // the label check's answer is this call's status
     RS_HIP(hipMemcpyAsync(&bad, c.flag, sizeof(bad), hipMemcpyDeviceToHost, st));
@@ -686,6 +685,11 @@ int run(rs_train* h, const char* fn, const float* d_x, const int32_t* d_labels, 
     if (bad) {
         set_error("%s: a label outside {0, 1}", fn);
         return RS_ERR_ARG;
+    }
+    if (backward) {                                         // the buffers rs_train_debug_copy reads are complete and this call's
+        h->last_ws = d_ws;
+        h->last_B = B;
+        h->last_L = L;
     }
     return RS_OK;
 }
@@ -842,7 +846,7 @@ size_t rs_train_workspace_bytes(const rs_train* h, int B, int L) {
 
 int rs_train_max_batch(const rs_train* h, int L) {
     if (!h || L < 1 || (L >> h->n_layers) < 1) return 0;
-    return std::min(max_batch_of(per_read_bytes(h->layers, L)), 65535);       // a grid's y extent
+    return std::min(max_batch_of(per_read_bytes(h->layers, L)), kMaxGridY);   // train_head_bwd_kernel has B in its grid's y
 }
 
 int rs_train_slice_plan(const rs_train* h, int layer, int B, int L, int32_t* n_slices, int32_t* slice_len) {
@@ -939,7 +943,8 @@ int rs_train_debug_copy(rs_train* h, int layer, int what, void* d_dst, size_t by
         return RS_ERR_ARG;
     }
     if (!h->last_ws) {
-        set_error("rs_train_debug_copy: no rs_train_forward_backward has run on this handle");
+        set_error("rs_train_debug_copy: no rs_train_forward_backward has run on this handle since the last rs_train_evaluate "
+                  "or refused call");
         return RS_ERR_ARG;
     }
     const Workspace w = plan_workspace(h->layers, h->last_B, h->last_L);

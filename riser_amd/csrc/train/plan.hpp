@@ -30,6 +30,7 @@ struct LayerShape {
 
 constexpr int kSlicePositions = 256;                    // a weight-gradient slice contracts about this many positions
 constexpr size_t kPartialBytes = size_t(32) << 20;      // and all slices' partial tiles of one conv stay below this
+constexpr int kMaxGridY = 65535;                        // a grid's y extent: the slices of a weight gradient, the reads of a batch
 constexpr int kTapGroup = 3;                            // taps one weight-gradient wave holds: k = 5 runs 3 + 2, k = 7 3 + 3 + 1
 
 inline int tap_groups(int k) { return (k + kTapGroup - 1) / kTapGroup; }
@@ -40,14 +41,15 @@ struct SlicePlan {
 };
 
 // Conv `s` contracts B * (L >> level) positions.  Slices of kSlicePositions, fewer where a conv's dW is so large that the
-// partials would outgrow kPartialBytes: long contractions have tiny dW, and the reverse.
+// partials would outgrow kPartialBytes: long contractions have tiny dW, and the reverse.  Never more than kMaxGridY: the
+// slices are the y extent of train_wgrad_kernel's grid, and the largest batch of long reads would ask for more.
 inline SlicePlan plan_slices(const LayerShape& s, int level, int B, int L) {
     const int64_t positions = (int64_t)B * (L >> level);
     const size_t tile_bytes = s.tile_floats() * sizeof(float);
     const int64_t cap = std::max<int64_t>(1, (int64_t)(kPartialBytes / tile_bytes));
     const int64_t want = (positions + kSlicePositions - 1) / kSlicePositions;
     SlicePlan p;
-    p.n_slices = (int)std::max<int64_t>(1, std::min(want, cap));
+    p.n_slices = (int)std::max<int64_t>(1, std::min({want, cap, (int64_t)kMaxGridY}));
     const int64_t len = (positions + p.n_slices - 1) / p.n_slices;
     p.slice_len = (int)((len + 3) / 4 * 4);
     p.n_slices = (int)std::max<int64_t>(1, (positions + p.slice_len - 1) / p.slice_len);

@@ -42,10 +42,10 @@ def constant_reads(B, L):
 
 def slice_plan(B, L, level, c_in, c_out, k):
     """csrc/train/plan.hpp's arithmetic: slices of about 256 positions, their partial tiles - (c_out c_in k + c_out) floats
-    each - within 32 MiB"""
+    each - within 32 MiB, and no more slices than a grid's y extent"""
     positions = B * (L >> level)
     cap = max(1, (32 << 20) // ((c_out * c_in * k + c_out) * 4))
-    n = max(1, min(-(-positions // 256), cap))
+    n = max(1, min(-(-positions // 256), cap, 65535))
     s = -(-(-(-positions // n)) // 4) * 4
     return max(1, -(-positions // s)), s
 
