@@ -1,6 +1,9 @@
 """Train the ConvNet on the GPU (riser/train.py; riser/nets/cnn.py:12-18,43-65 with `gap_fc`, two classes): forward,
-cross-entropy, backward and Adam are the HIP kernels of csrc/train.hip (rs_train_*).  `Trainer` is the shipped class (depth 1,
-every kernel 3), `GenericTrainer` any `depth` and any odd `kernels` - every net riser_amd.gconv runs; `trainer_for` picks.
+cross-entropy, backward and Adam are the HIP kernels of csrc/train.hip (rs_train_*).  A net is (channels, kernels, depth), read
+from a config by `net_of`; `param_keys`, `param_shapes`, `init_state` and `create_handle` take it, the shipped class - depth 1,
+every kernel 3 - being their default.  `Trainer` is the shipped class (`check_config`, rs_train_create), `GenericTrainer` the
+same body for any `depth` and any odd `kernels` - every net riser_amd.gconv runs (`check_generic_config`,
+rs_train_create_generic); `trainer_for` picks.
 
     python -m riser_amd.train EXP_DIR DATA_DIR CHECKPT|None CONFIG.yaml START_EPOCH
 
@@ -30,67 +33,56 @@ ADAM = dict(beta1=0.9, beta2=0.999, eps=1e-8)      # torch.optim.Adam's defaults
 METRICS = ("epoch", "train_loss", "val_loss", "val_acc", "train_t", "val_t", "train - val loss")     # riser/train.py:226-231
 
 
-def check_config(config) -> list:
-    """the channel list of a config this module trains; ValueError - before any GPU call - for everything else"""
+def net_of(config):
+    """(channels, kernels, depth) of a config - the one description of the net - behind the checks every trainer shares: the
+    `cnn` model, fp32, the `gap_fc` head, two classes, lists as long as n_layers >= 1; ValueError for everything else"""
     model = getattr(config, "model", "cnn")
     if model != "cnn":
         raise ValueError(f"model {model!r}: riser_amd.train trains the `cnn` model only")
+    dtype = getattr(config, "dtype", "f32")
+    if dtype not in ("f32", "fp32", "float32"):
+        raise ValueError(f"dtype {dtype!r}: riser_amd.train is fp32 only")
     cnn = config.cnn
     n_layers, depth = int(cnn.n_layers), int(getattr(cnn, "depth", 1))
     channels, kernels = [int(v) for v in cnn.channels], [int(v) for v in cnn.kernels]
-    if depth != 1:
-        raise ValueError(f"depth {depth}: riser_amd.train trains depth 1 only")
     if n_layers < 1 or len(channels) < n_layers or len(kernels) < n_layers:
         raise ValueError(f"channels {channels} / kernels {kernels}: shorter than n_layers {n_layers} >= 1")
-    if any(k != 3 for k in kernels[:n_layers]):
-        raise ValueError(f"kernels {kernels[:n_layers]}: riser_amd.train trains kernels of 3 only")
     classifier = getattr(cnn, "classifier", "gap_fc")
     if classifier != "gap_fc":
         raise ValueError(f"classifier {classifier!r}: riser_amd.train trains the `gap_fc` head only")
     if int(cnn.n_classes) != 2:
         raise ValueError("riser_amd.train trains two-class heads only")
-    dtype = getattr(config, "dtype", "f32")
-    if dtype not in ("f32", "fp32", "float32"):
-        raise ValueError(f"dtype {dtype!r}: riser_amd.train is fp32 only")
-    return channels[:n_layers]
+    return channels[:n_layers], kernels[:n_layers], depth
+
+
+def check_config(config) -> list:
+    """the channel list of a config of the shipped class (depth 1, every kernel 3); ValueError - before any GPU call - for
+    everything else"""
+    channels, kernels, depth = net_of(config)
+    if depth != 1:
+        raise ValueError(f"depth {depth}: riser_amd.train.Trainer trains depth 1 only")
+    if any(k != 3 for k in kernels):
+        raise ValueError(f"kernels {kernels}: riser_amd.train.Trainer trains kernels of 3 only")
+    return channels
 
 
 def check_generic_config(config):
     """(channels, kernels, depth) of a config GenericTrainer trains - what the generic inference family (riser_amd.gconv)
-    runs: any depth >= 1, every kernel odd, `gap_fc`, two classes, fp32; ValueError - before any GPU call - for everything
-    else, a conv that fits no tile shape of that family included"""
+    runs: 1-16 layers of depth 1-64, every kernel odd; ValueError - before any GPU call - for everything else, a conv that
+    fits no tile shape of that family included"""
     from .gconv import layer_plan
-    model = getattr(config, "model", "cnn")
-    if model != "cnn":
-        raise ValueError(f"model {model!r}: riser_amd.train trains the `cnn` model only")
-    dtype = getattr(config, "dtype", "f32")
-    if dtype not in ("f32", "fp32", "float32"):
-        raise ValueError(f"dtype {dtype!r}: riser_amd.train is fp32 only")
-    cnn = config.cnn
-    n_layers, depth = int(cnn.n_layers), int(getattr(cnn, "depth", 1))
-    channels, kernels = [int(v) for v in cnn.channels], [int(v) for v in cnn.kernels]
-    if n_layers < 1 or n_layers > 16 or depth < 1 or depth > 64:
-        raise ValueError(f"n_layers {n_layers} / depth {depth}: riser_amd.train trains 1-16 layers of depth 1-64")
-    if len(channels) < n_layers or len(kernels) < n_layers:
-        raise ValueError(f"channels {channels} / kernels {kernels}: shorter than n_layers {n_layers}")
-    channels, kernels = channels[:n_layers], kernels[:n_layers]
+    channels, kernels, depth = net_of(config)
+    if len(channels) > 16 or depth < 1 or depth > 64:
+        raise ValueError(f"n_layers {len(channels)} / depth {depth}: riser_amd.train trains 1-16 layers of depth 1-64")
     if any(k < 1 or k % 2 == 0 for k in kernels):
         raise ValueError(f"kernels {kernels}: even conv kernels ('same' pads them asymmetrically) are not supported")
     if any(c < 1 for c in channels):
         raise ValueError(f"channels {channels}: every layer needs at least one")
-    classifier = getattr(cnn, "classifier", "gap_fc")
-    if classifier != "gap_fc":
-        raise ValueError(f"classifier {classifier!r}: riser_amd.train trains the `gap_fc` head only")
-    if int(cnn.n_classes) != 2:
-        raise ValueError("riser_amd.train trains two-class heads only")
-    c_in = 1
-    for c, k in zip(channels, kernels):
-        for _ in range(depth):
-            try:
-                layer_plan(c_in, c, k)
-            except nv.NativeError as e:
-                raise ValueError(f"conv {c_in} -> {c}, kernel {k}: the generic ConvNet family could not run it ({e})") from None
-            c_in = c
+    for _, c_in, c, k in _convs(channels, kernels, depth):
+        try:
+            layer_plan(c_in, c, k)
+        except nv.NativeError as e:
+            raise ValueError(f"conv {c_in} -> {c}, kernel {k}: the generic ConvNet family could not run it ({e})") from None
     return channels, kernels, depth
 
 
@@ -104,73 +96,45 @@ def is_shipped_class(config) -> bool:
         return False
 
 
-def generic_param_keys(n_layers: int, depth: int) -> list:
-    """the reference's state-dict keys in the order of the tensor index: conv j = layer * depth + d is layers.{layer}.{2 d}
-    (nn.Sequential of conv, ReLU, conv, ReLU, ..., MaxPool1d: riser/nets/cnn.py:52-65)"""
-    keys = []
-    for i in range(n_layers):
+def _convs(channels, kernels=None, depth=1):
+    """(state-dict key prefix, c_in, c_out, k) of every conv in launch order, j = layer * depth + d: layers.{layer}.{2 d}
+    (nn.Sequential of conv, ReLU, conv, ReLU, ..., MaxPool1d: riser/nets/cnn.py:52-65).  kernels None: every kernel 3."""
+    c_in = 1
+    for i, c in enumerate(channels):
         for d in range(depth):
-            keys += [f"layers.{i}.{2 * d}.weight", f"layers.{i}.{2 * d}.bias"]
-    return keys + ["classifier.2.weight", "classifier.2.bias"]
-
-
-def generic_param_shapes(channels, kernels, depth) -> dict:
-    shapes, c_in = {}, 1
-    for i, (c, k) in enumerate(zip(channels, kernels)):
-        for d in range(depth):
-            shapes[f"layers.{i}.{2 * d}.weight"], shapes[f"layers.{i}.{2 * d}.bias"] = (c, c_in, k), (c,)
+            yield f"layers.{i}.{2 * d}", c_in, c, 3 if kernels is None else kernels[i]
             c_in = c
-    shapes["classifier.2.weight"], shapes["classifier.2.bias"] = (2, c_in), (2,)
-    return shapes
 
 
-def generic_init_state(channels, kernels, depth) -> dict:
-    """torch's own initialisation of nn.Conv1d / nn.Linear tensors of the net's shapes, on the CPU, in the reference's
-    construction order"""
-    sd, c_in = {}, 1
-    for i, (c, k) in enumerate(zip(channels, kernels)):
-        for d in range(depth):
-            conv = torch.nn.Conv1d(c_in, c, k)
-            sd[f"layers.{i}.{2 * d}.weight"], sd[f"layers.{i}.{2 * d}.bias"] = conv.weight.detach(), conv.bias.detach()
-            c_in = c
-    fc = torch.nn.Linear(c_in, 2)
-    sd["classifier.2.weight"], sd["classifier.2.bias"] = fc.weight.detach(), fc.bias.detach()
-    return sd
-
-
-def param_keys(n_layers: int) -> list:
+def param_keys(n_layers: int, depth: int = 1) -> list:
     """the reference's state-dict keys in the order of rs_train_get_params' tensor index"""
-    keys = []
-    for i in range(n_layers):
-        keys += [f"layers.{i}.0.weight", f"layers.{i}.0.bias"]
-    return keys + ["classifier.2.weight", "classifier.2.bias"]
+    return list(param_shapes([1] * n_layers, None, depth))
 
 
-def param_shapes(channels) -> dict:
-    shapes, c_in = {}, 1
-    for i, c in enumerate(channels):
-        shapes[f"layers.{i}.0.weight"], shapes[f"layers.{i}.0.bias"] = (c, c_in, 3), (c,)
-        c_in = c
-    shapes["classifier.2.weight"], shapes["classifier.2.bias"] = (2, c_in), (2,)
+def param_shapes(channels, kernels=None, depth=1) -> dict:
+    shapes = {}
+    for key, c_in, c, k in _convs(channels, kernels, depth):
+        shapes[key + ".weight"], shapes[key + ".bias"] = (c, c_in, k), (c,)
+    shapes["classifier.2.weight"], shapes["classifier.2.bias"] = (2, channels[-1]), (2,)
     return shapes
 
 
-def init_state(channels) -> dict:
-    """torch's own initialisation of nn.Conv1d / nn.Linear tensors of the net's shapes, on the CPU"""
-    sd, c_in = {}, 1
-    for i, c in enumerate(channels):
-        conv = torch.nn.Conv1d(c_in, c, 3)
-        sd[f"layers.{i}.0.weight"], sd[f"layers.{i}.0.bias"] = conv.weight.detach(), conv.bias.detach()
-        c_in = c
-    fc = torch.nn.Linear(c_in, 2)
+def init_state(channels, kernels=None, depth=1) -> dict:
+    """torch's own initialisation of nn.Conv1d / nn.Linear tensors of the net's shapes, on the CPU, in the reference's
+    construction order: conv by conv as they launch, then the head"""
+    sd = {}
+    for key, c_in, c, k in _convs(channels, kernels, depth):
+        conv = torch.nn.Conv1d(c_in, c, k)
+        sd[key + ".weight"], sd[key + ".bias"] = conv.weight.detach(), conv.bias.detach()
+    fc = torch.nn.Linear(channels[-1], 2)
     sd["classifier.2.weight"], sd["classifier.2.bias"] = fc.weight.detach(), fc.bias.detach()
     return sd
 
 
-def _checked_state(state, channels, shapes=None) -> dict:
+def _checked_state(state, shapes) -> dict:
     sd = load_state(state)
     out = {}
-    for key, shape in (shapes if shapes is not None else param_shapes(channels)).items():
+    for key, shape in shapes.items():
         if key not in sd:
             raise ValueError(f"state dict has no {key!r}")
         a = np.ascontiguousarray(sd[key], dtype=np.float32)
@@ -181,25 +145,30 @@ def _checked_state(state, channels, shapes=None) -> dict:
 
 
 class Trainer:
-    """The net's parameters, their gradients and the Adam moments on the device (rs_train_*).  x: float32 [B, L] on the
-    device or the host, y: any integer tensor of B labels in {0, 1}.  A batch beyond max_batch(L) is refused, not split: a
-    split would change the mean."""
+    """The net's parameters, their gradients and the Adam moments on the device (rs_train_*), for the shipped class: depth 1,
+    every kernel 3 (rs_train_create).  x: float32 [B, L] on the device or the host, y: any integer tensor of B labels in
+    {0, 1}.  A batch beyond max_batch(L) is refused, not split: a split would change the mean.  Where a method takes `layer` it
+    means the conv index j = layer * depth + d, as the C ABI does."""
+
+    generic = False                                         # which config check applies and which constructor is reached
 
     def __init__(self, config, state_dict=None, device=None, dtype: str = "f32"):
         if dtype not in ("f32", "fp32", "float32"):
             raise ValueError(f"dtype {dtype!r}: riser_amd.train is fp32 only")
-        self.channels = check_config(config)
-        self.learning_rate = float(getattr(config, "learning_rate", 1e-3))
         self._h = None
         self._ws = None
-        keep = _checked_state(state_dict if state_dict is not None else init_state(self.channels), self.channels)
+        (check_generic_config if self.generic else check_config)(config)
+        self.channels, self.kernels, self.depth = net_of(config)
+        self.learning_rate = float(getattr(config, "learning_rate", 1e-3))
+        self.n_layers = len(self.channels)
+        self._keys = param_keys(self.n_layers, self.depth)
+        self._shapes = param_shapes(self.channels, self.kernels, self.depth)
+        keep = _checked_state(state_dict if state_dict is not None else init_state(self.channels, self.kernels, self.depth),
+                              self._shapes)
         nv.require_gpu()
         d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
-        self.n_layers = len(self.channels)
-        self._keys = param_keys(self.n_layers)
-        self._shapes = param_shapes(self.channels)
-        self._h = create_handle(self.channels, keep, self.device.index)
+        self._h = create_handle(self.channels, keep, self.device.index, self.kernels, self.depth, generic=self.generic)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -217,7 +186,7 @@ class Trainer:
         return int(nv.lib().rs_train_max_batch(self._h, int(L)))
 
     def slice_plan(self, layer: int, B: int, L: int):
-        """(slices, positions per slice) of layer `layer`'s weight-gradient contraction (rs_train_slice_plan)"""
+        """(slices, positions per slice) of conv `layer`'s weight-gradient contraction (rs_train_slice_plan)"""
         n, s = C.c_int32(), C.c_int32()
         nv.check(nv.lib().rs_train_slice_plan(self._h, int(layer), int(B), int(L), C.byref(n), C.byref(s)), "rs_train_slice_plan")
         return int(n.value), int(s.value)
@@ -279,53 +248,18 @@ class Trainer:
         return out
 
     def state_dict(self) -> dict:
-        """the reference's keys as CPU fp32 tensors (riser/nets/cnn.py's state dict at depth 1 with `gap_fc`)"""
+        """the reference's keys as CPU fp32 tensors (riser/nets/cnn.py's state dict at this depth with `gap_fc`)"""
         return self._tensors("rs_train_get_params")
 
     def load_state_dict(self, state):
-        sd = _checked_state(state, self.channels, self._shapes)
+        sd = _checked_state(state, self._shapes)
         for i, key in enumerate(self._keys):
             nv.check(nv.lib().rs_train_set_params(self._h, i, sd[key].ctypes.data, sd[key].size), "rs_train_set_params")
 
     def debug_copy(self, layer: int, what: str, B: int, L: int) -> torch.Tensor:
-        """layer's 'y' (pooled rows), 'sel' (selectors) or 'dy' (incoming gradient) of the last forward + backward, which ran B
-        reads of L samples: [B, L >> (layer + 1), c_out] on the host (rs_train_debug_copy)"""
-        c = self.channels[layer]
-        cp, rows = (c + 3) & ~3, L >> (layer + 1)
-        dst = torch.empty((B, rows, cp), dtype=torch.uint8 if what == "sel" else torch.float32, device=self.device)
-        nv.check(nv.lib().rs_train_debug_copy(self._h, layer, {"y": 0, "sel": 1, "dy": 2}[what], dst.data_ptr(),
-                                              dst.numel() * dst.element_size()), "rs_train_debug_copy")
-        return dst[:, :, :c].cpu()
-
-
-class GenericTrainer(Trainer):
-    """Trainer's surface for any depth and any odd kernels (rs_train_create_generic).  Where a method takes `layer` it means
-    the conv index j = layer * depth + d, as the C ABI does."""
-
-    def __init__(self, config, state_dict=None, device=None, dtype: str = "f32"):
-        if dtype not in ("f32", "fp32", "float32"):
-            raise ValueError(f"dtype {dtype!r}: riser_amd.train is fp32 only")
-        self._h = None
-        self._ws = None
-        self.channels, self.kernels, self.depth = check_generic_config(config)
-        self.learning_rate = float(getattr(config, "learning_rate", 1e-3))
-        self.n_layers = len(self.channels)
-        self._keys = generic_param_keys(self.n_layers, self.depth)
-        self._shapes = generic_param_shapes(self.channels, self.kernels, self.depth)
-        keep = _checked_state(state_dict if state_dict is not None
-                              else generic_init_state(self.channels, self.kernels, self.depth), self.channels, self._shapes)
-        nv.require_gpu()
-        d = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
-        self._h = create_generic_handle(self.channels, self.kernels, self.depth, keep, self.device.index)
-
-    def state_dict(self) -> dict:
-        """the reference's keys as CPU fp32 tensors (riser/nets/cnn.py's state dict at this depth with `gap_fc`)"""
-        return self._tensors("rs_train_get_params")
-
-    def debug_copy(self, layer: int, what: str, B: int, L: int) -> torch.Tensor:
         """conv `layer`'s 'y' (the last conv of a layer: pooled rows; an inner conv: its ReLU rows), 'sel' (selectors, pooling
-        convs only) or 'dy' (the gradient arriving at 'y') of the last forward + backward of B reads of L samples, on the host"""
+        convs only) or 'dy' (the gradient arriving at 'y') of the last forward + backward of B reads of L samples, on the host:
+        [B, rows, c_out], at depth 1 rows = L >> (layer + 1) (rs_train_debug_copy)"""
         level, pools = layer // self.depth, layer % self.depth == self.depth - 1
         c = self.channels[level]
         cp, rows = (c + 3) & ~3, (L >> level) >> (1 if pools else 0)
@@ -333,6 +267,12 @@ class GenericTrainer(Trainer):
         nv.check(nv.lib().rs_train_debug_copy(self._h, layer, {"y": 0, "sel": 1, "dy": 2}[what], dst.data_ptr(),
                                               dst.numel() * dst.element_size()), "rs_train_debug_copy")
         return dst[:, :, :c].cpu()
+
+
+class GenericTrainer(Trainer):
+    """Trainer for any depth and any odd kernels - every net check_generic_config takes (rs_train_create_generic)"""
+
+    generic = True
 
 
 def trainer_for(config, state_dict=None, device=None):
@@ -343,33 +283,23 @@ def trainer_for(config, state_dict=None, device=None):
     return GenericTrainer(config, state_dict, device)
 
 
-def create_generic_handle(channels, kernels, depth, state, device_index: int):
-    """rs_train_create_generic on the arrays of `state` ({reference key: float32 array}); device_index < 0 as create_handle"""
-    convs = (_Conv * (len(channels) * depth))()
-    c_in = 1
-    for i, (c, k) in enumerate(zip(channels, kernels)):
-        for d in range(depth):
-            convs[i * depth + d] = _Conv(c_in, c, k, 0, state[f"layers.{i}.{2 * d}.weight"].ctypes.data,
-                                         state[f"layers.{i}.{2 * d}.bias"].ctypes.data)
-            c_in = c
+def create_handle(channels, state, device_index: int, kernels=None, depth=1, generic=None):
+    """a C handle on the arrays of `state` ({reference key: float32 array}): rs_train_create for the shipped class (depth 1,
+    every kernel 3), rs_train_create_generic for every other net - the two keep their own limits - or as `generic` says.
+    device_index < 0: a handle without device memory, which answers the plan functions and the argument checks on a machine
+    without a GPU"""
+    specs = list(_convs(channels, kernels, depth))
+    convs = (_Conv * len(specs))(*[_Conv(c_in, c, k, 0, state[key + ".weight"].ctypes.data, state[key + ".bias"].ctypes.data)
+                                   for key, c_in, c, k in specs])
+    head = state["classifier.2.weight"].ctypes.data, state["classifier.2.bias"].ctypes.data
+    if generic is None:
+        generic = depth != 1 or any(k != 3 for _, _, _, k in specs)
     h = C.c_void_p()
-    nv.check(nv.lib().rs_train_create_generic(convs, len(channels), int(depth), state["classifier.2.weight"].ctypes.data,
-                                              state["classifier.2.bias"].ctypes.data, int(device_index), C.byref(h)),
-             "rs_train_create_generic")
-    return h
-
-
-def create_handle(channels, state, device_index: int):
-    """rs_train_create on the arrays of `state` ({reference key: float32 array}); device_index < 0: a handle without device
-    memory, which answers the plan functions and the argument checks on a machine without a GPU"""
-    convs = (_Conv * len(channels))()
-    c_in = 1
-    for i, c in enumerate(channels):
-        convs[i] = _Conv(c_in, c, 3, 0, state[f"layers.{i}.0.weight"].ctypes.data, state[f"layers.{i}.0.bias"].ctypes.data)
-        c_in = c
-    h = C.c_void_p()
-    nv.check(nv.lib().rs_train_create(convs, len(channels), state["classifier.2.weight"].ctypes.data,
-                                      state["classifier.2.bias"].ctypes.data, int(device_index), C.byref(h)), "rs_train_create")
+    if generic:
+        nv.check(nv.lib().rs_train_create_generic(convs, len(channels), int(depth), *head, int(device_index), C.byref(h)),
+                 "rs_train_create_generic")
+    else:
+        nv.check(nv.lib().rs_train_create(convs, len(channels), *head, int(device_index), C.byref(h)), "rs_train_create")
     return h
 
 

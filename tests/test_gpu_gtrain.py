@@ -3,92 +3,35 @@ on the device against float64.
 
 Gap = largest absolute difference over a tensor / largest magnitude of the float64 tensor.  The bar of a tensor is four times
 the gap torch's own fp32 autograd, run on the CPU, shows against float64 on the same inputs, with a floor of 1e-6; it is
-computed here at run time (gtrain_ref.bars_of) and never taken from the code under test.  Where a case has fragile elements
-(gtrain_ref.fragile) the backward kernels are held to the numpy float64 backward fed the DEVICE's selectors and gates, and the
-device's decisions must equal float64's outside the fragile set.  Convs are numbered j = layer * depth + d.  Measured gaps and
+computed here at run time (train_ref.bars_of) and never taken from the code under test.  Where a case has fragile elements
+(train_ref.fragile) the backward kernels are held to the numpy float64 backward fed the DEVICE's selectors and gates, and the
+device's decisions must equal float64's outside the fragile set.  Convs are numbered j = layer * depth + d; the device helpers are
+train_device's.  Measured gaps and
 bars: profiles/gtrain_gpu_tests.txt, DESIGN.md section 17.
 """
-import types
-
 import numpy as np
 import pytest
 import torch
 
-import gtrain_ref as G
-from riser_amd import synth
-
-
-def config_of(channels, kernels, depth, lr=1e-3):
-    return types.SimpleNamespace(model="cnn", learning_rate=lr, cnn=synth.CnnConfig(channels=channels, kernels=kernels, depth=depth))
-
-
-def trainer_of(name_or_shape, sd, lr=1e-3):
-    from riser_amd.train import GenericTrainer
-    channels, kernels, depth = G.CASES[name_or_shape][:3] if isinstance(name_or_shape, str) else name_or_shape
-    return GenericTrainer(config_of(channels, kernels, depth, lr), sd, device=torch.device("cuda", 0))
-
-
-def run_device(shape, sd, x, y, debug=False):
-    """-> loss, {key: grad as float64 numpy}, and with debug the device's per-conv (sel | None, gate, dy)"""
-    t = trainer_of(shape, sd)
-    try:
-        loss, grads = t.loss_and_grads(torch.from_numpy(x), torch.from_numpy(y))
-        grads = {k: v.numpy().astype(np.float64) for k, v in grads.items()}
-        if not debug:
-            return loss, grads
-        B, L = x.shape
-        pools = [p for _, p in G.conv_keys(sd)]
-        sel = [t.debug_copy(j, "sel", B, L).numpy() if p else None for j, p in enumerate(pools)]
-        gate = [t.debug_copy(j, "y", B, L).numpy() > 0 for j in range(len(pools))]
-        dy = [t.debug_copy(j, "dy", B, L).numpy().astype(np.float64) for j in range(len(pools))]
-        return loss, grads, sel, gate, dy
-    finally:
-        t.close()
-
-
-def check(name, got, want, bar):
-    gap = G.gap_of(got, want)
-    print(f"{name}: gap {gap:.3e} bar {bar:.3e}")
-    return gap <= bar, f"{name}: gap {gap:.3e} > bar {bar:.3e}"
-
-
-def assert_all(results):
-    bad = [msg for ok, msg in results if not ok]
-    assert not bad, "\n".join(bad)
+import train_device as D
+import train_ref as R
+from train_device import assert_all, check, config_of, run_device, trainer_of
 
 
 def against_autograd(name):
     """a case without fragile elements: the loss and every gradient against float64 autograd"""
-    sd, x, y = G.case_of(name)
-    bars, _, loss_bar, _, (l64, g64, _, _) = G.bars_of(sd, x, y)
-    assert G.fragile_share(G.forward64(sd, x)) == 0
+    sd, x, y = R.case_of(name)
+    bars, _, loss_bar, _, (l64, g64, _, _) = R.bars_of(sd, x, y)
+    assert R.fragile_share(R.forward64(sd, x)) == 0
     loss, grads = run_device(name, sd, x, y)
     print(f"{name} loss: device {loss!r} float64 {l64!r} bar {loss_bar:.3e}")
     assert abs(loss - l64) <= loss_bar * abs(l64)
     assert_all([check(f"{name} {k}", grads[k], g64[k], bars[k]) for k in g64])
 
 
-def held_to_numpy_backward(name, sd=None, x=None, y=None):
-    """the backward kernels against the numpy backward fed the device's decisions, which equal float64's outside the fragile
-    elements -> (device grads, numpy grads, bars)"""
-    if sd is None:
-        sd, x, y = G.case_of(name)
-    bars, dbars, loss_bar, _, (l64, _, _, _) = G.bars_of(sd, x, y)
-    fwd = G.forward64(sd, x)
-    frag = G.fragile(fwd)
-    loss, grads, sel, gate, dy = run_device(name, sd, x, y, debug=True)
-    for j in range(len(sel)):
-        if sel[j] is not None:
-            differs = (sel[j] != fwd["sel"][j]) & fwd["gate"][j] & gate[j]          # a selector matters where a gradient flows
-            assert not (differs & ~frag[j]).any(), f"conv {j}: a selector differs from float64's outside the fragile elements"
-        assert gate[j].shape == fwd["gate"][j].shape, j
-        assert not ((gate[j] != fwd["gate"][j]) & ~frag[j]).any(), f"conv {j}: a gate differs outside the fragile elements"
-    g_ref, dy_ref = G.backward64(sd, fwd, y, sels=sel, gates=gate)
-    print(f"{name} loss: device {loss!r} float64 {l64!r} bar {loss_bar:.3e}")
-    assert abs(loss - l64) <= loss_bar * abs(l64)
-    assert_all([check(f"{name} {k}", grads[k], g_ref[k], bars[k]) for k in g_ref] +
-               [check(f"{name} dY_{j}", dy[j], dy_ref[j], dbars[j]) for j in range(len(sel))])
-    return grads, g_ref, bars
+def held_to_numpy_backward(name):
+    sd, x, y = R.case_of(name)
+    return D.held_to_numpy_backward(name, sd, x, y, label=f"{name} ")
 
 
 @pytest.mark.gpu
@@ -116,8 +59,8 @@ def test_tap_groups(k):
 def test_bias_gradient_is_the_same_whatever_the_group_count():
     """a kernel-1 net, and the same net as kernel 5 and kernel 7 with zeros around the centre tap: the forward pass adds exact
     zeros, dZ is the same, so db - written by the first tap group only - and the centre tap of dW keep their bits"""
-    sd1, x, y = G.case_of("taps1")
-    channels = G.CASES["taps1"][0]
+    sd1, x, y = R.case_of("taps1")
+    channels = R.CASES["taps1"][0]
     got = {}
     for k in (1, 5, 7):
         sd = {key: v.copy() for key, v in sd1.items()}
@@ -140,14 +83,14 @@ def test_bias_gradient_is_the_same_whatever_the_group_count():
 
 @pytest.mark.gpu
 def test_slice_boundaries():
-    channels, kernels, depth, B, L, _ = G.CASES["slices"]
-    sd, x, y = G.case_of("slices")
+    channels, kernels, depth, B, L, _ = R.CASES["slices"]
+    sd, x, y = R.case_of("slices")
     t = trainer_of("slices", sd)
     try:
         plans = [t.slice_plan(j, B, L) for j in range(len(channels) * depth)]
     finally:
         t.close()
-    assert plans == [G.slice_plan(B, L, level, ci, co, k) for level, ci, co, k in G.convs_of(channels, kernels, depth)]
+    assert plans == [R.slice_plan(B, L, level, ci, co, k) for level, ci, co, k in R.convs_of(channels, kernels, depth)]
     n, s = plans[0]
     assert n >= 3 and s % 4 == 0 and (n - 1) * s < B * L < n * s, (n, s)           # several slices, the last one not full
     held_to_numpy_backward("slices")
@@ -160,13 +103,13 @@ def test_block_boundary():
 
 @pytest.mark.gpu
 def test_exact_ties_and_dead_units():
-    cases = {name: (sd, x, y) for name, sd, x, y in G.special_cases()}
-    shape = G.CASES["depth2"][:3]
+    cases = {name: (sd, x, y) for name, sd, x, y in R.special_cases()}
+    shape = R.CASES["depth2"][:3]
     sd, x, y = cases["ties"]
-    fwd = G.forward64(sd, x)
+    fwd = R.forward64(sd, x)
     z = fwd["z"][1]                                          # the first pooling conv
     assert (z[:, 0:-1:2] == z[:, 1::2]).mean() >= 0.9
-    bars, _, loss_bar, _, (l64, g64, _, _) = G.bars_of(sd, x, y)
+    bars, _, loss_bar, _, (l64, g64, _, _) = R.bars_of(sd, x, y)
     loss, grads, sel, gate, _ = run_device(shape, sd, x, y, debug=True)
     for j, s in enumerate(sel):
         if s is not None:
@@ -176,8 +119,8 @@ def test_exact_ties_and_dead_units():
     assert abs(loss - l64) <= loss_bar * abs(l64)
     assert_all([check(f"ties {k}", grads[k], g64[k], bars[k]) for k in g64])
     sd, x, y = cases["dead"]
-    fwd = G.forward64(sd, x)
-    _, g64, _, _ = G.torch_loss_and_grads(sd, x, y)
+    fwd = R.forward64(sd, x)
+    _, g64, _, _ = R.torch_loss_and_grads(sd, x, y)
     loss, grads, sel, gate, _ = run_device(shape, sd, x, y, debug=True)
     assert np.isfinite(loss) and all(np.isfinite(g).all() for g in grads.values())
     for j, s in enumerate(sel):
@@ -187,14 +130,14 @@ def test_exact_ties_and_dead_units():
         if not g64[k].any():
             assert not g.any(), k
     assert all(not g64[k].any() for k in g64 if k.startswith("layers.") or k == "classifier.2.weight")
-    assert G.gap_of(grads["classifier.2.bias"], g64["classifier.2.bias"]) <= 1e-6
+    assert R.gap_of(grads["classifier.2.bias"], g64["classifier.2.bias"]) <= 1e-6
 
 
 @pytest.mark.gpu
 def test_five_adam_steps_against_torch_float64():
-    sd, x, y = G.case_of("depth2")
-    l64, p64 = G.torch_adam(sd, x, y, torch.float64, 5, 1e-3)
-    l32, p32 = G.torch_adam(sd, x, y, torch.float32, 5, 1e-3)
+    sd, x, y = R.case_of("depth2")
+    l64, p64 = R.torch_adam(sd, x, y, torch.float64, 5, 1e-3)
+    l32, p32 = R.torch_adam(sd, x, y, torch.float32, 5, 1e-3)
     t = trainer_of("depth2", sd, lr=1e-3)
     losses = [t.step(torch.from_numpy(x), torch.from_numpy(y)) for _ in range(5)]
     got = {k: v.numpy() for k, v in t.state_dict().items()}
@@ -203,12 +146,12 @@ def test_five_adam_steps_against_torch_float64():
         bar = max(4 * abs(l32[i] - l64[i]) / abs(l64[i]), 1e-6)
         print(f"step {i}: loss {losses[i]!r} float64 {l64[i]!r} bar {bar:.3e}")
         assert abs(losses[i] - l64[i]) <= bar * abs(l64[i]), i
-    assert_all([check(f"adam {k}", got[k], p64[k], max(4 * G.gap_of(p32[k], p64[k]), 1e-6)) for k in p64])
+    assert_all([check(f"adam {k}", got[k], p64[k], max(4 * R.gap_of(p32[k], p64[k]), 1e-6)) for k in p64])
 
 
 @pytest.mark.gpu
 def test_same_state_and_batch_give_the_same_bits():
-    sd, x, y = G.case_of("slices")
+    sd, x, y = R.case_of("slices")
     xs, ys = torch.from_numpy(x), torch.from_numpy(y)
     t = trainer_of("slices", sd)
     l1, g1 = t.loss_and_grads(xs, ys)
@@ -225,14 +168,12 @@ def test_same_state_and_batch_give_the_same_bits():
 
 @pytest.mark.gpu
 def test_generic_constructor_gives_the_shipped_class_its_bits():
-    import train_ref as R
-    from riser_amd.train import Trainer
-    channels = [3, 7, 18, 37]
-    sd = R.make_state(channels, 11)
+    from riser_amd.train import GenericTrainer, Trainer
+    shape = ([3, 7, 18, 37], [3] * 4, 1)
+    sd = R.make_state(*shape, 11)
     x, y = R.make_batch(3, 100, 111)
     xs, ys = torch.from_numpy(x), torch.from_numpy(y)
-    ours = trainer_of((channels, [3] * 4, 1), sd)
-    ref = Trainer(config_of(channels, [3] * 4, 1), sd, device=torch.device("cuda", 0))
+    ours, ref = trainer_of(shape, sd, cls=GenericTrainer), trainer_of(shape, sd, cls=Trainer)
     try:
         (la, ga), (lb, gb) = ours.loss_and_grads(xs, ys), ref.loss_and_grads(xs, ys)
         assert la == lb and list(ga) == list(gb) and all(torch.equal(ga[k], gb[k]) for k in ga)
@@ -248,8 +189,8 @@ def test_generic_constructor_gives_the_shipped_class_its_bits():
 @pytest.mark.gpu
 def test_checkpoint_loads_into_the_inference_family(tmp_path):
     from riser_amd.gconv import GConvNet, build_gconv_program
-    channels, kernels, depth = G.CASES["depth2"][:3]
-    sd, x, y = G.case_of("depth2")
+    channels, kernels, depth = R.CASES["depth2"][:3]
+    sd, x, y = R.case_of("depth2")
     xs, ys = torch.from_numpy(x), torch.from_numpy(y)
     t = trainer_of("depth2", sd)
     t.step(xs, ys)
@@ -260,7 +201,7 @@ def test_checkpoint_loads_into_the_inference_family(tmp_path):
     assert list(state) == list(sd) and all(v.dtype == torch.float32 and v.device.type == "cpu" for v in state.values())
     assert any(not np.array_equal(state[k].numpy(), sd[k]) for k in sd)
     stepped = {k: v.numpy() for k, v in state.items()}
-    _, _, _, logits_bar, (_, _, _, lg64) = G.bars_of(stepped, x, y)
+    _, _, _, logits_bar, (_, _, _, lg64) = R.bars_of(stepped, x, y)
     dev = torch.device("cuda", 0)
     net = GConvNet(build_gconv_program(str(tmp_path / "depth2_latest_model.pth"), config_of(channels, kernels, depth).cnn), dev)
     try:

@@ -3,10 +3,10 @@ function of the handle's state and that call's batch alone - never of the calls 
 padded row pitch - and the paths a real fit() takes beside the backward kernels (evaluate, the loss edges, the label check,
 load_state_dict, Adam by itself) against float64.
 
-Every test runs once on the shipped class (`Trainer`, channels [3, 7, 18, 37]) and once on gtrain_ref.CASES["depth2"]
+Every test runs once on the shipped class (`Trainer`, channels [3, 7, 18, 37]) and once on train_ref.CASES["depth2"]
 (`GenericTrainer`), at B <= 16 and L <= 1001.  Bit equality (`==`, torch.equal) is the bar wherever two runs of the same
 arithmetic are compared: csrc/train/plan.hpp makes every sum a function of (B, L, shapes) alone, and
-test_same_state_and_batch_give_the_same_bits holds run-to-run determinism.  Against float64 the bars are gtrain_ref.bars_of's:
+test_same_state_and_batch_give_the_same_bits holds run-to-run determinism.  Against float64 the bars are train_ref.bars_of's:
 four times the gap of torch's own fp32 CPU run, floor 1e-6, computed here at run time and never from the device.  Measured
 gaps and bars: profiles/train_calls_gpu_tests.txt, DESIGN.md sections 16 and 17.
 """
@@ -16,22 +16,11 @@ import numpy as np
 import pytest
 import torch
 
-import gtrain_ref as G
 import train_calls_ref as T
 import train_ref as R
+from train_device import assert_all, check
 
 kinds = pytest.mark.parametrize("kind", T.KINDS)
-
-
-def check(name, got, want, bar):
-    gap = R.gap_of(got, want)
-    print(f"{name}: gap {gap:.3e} bar {bar:.3e}")
-    return gap <= bar, f"{name}: gap {gap:.3e} > bar {bar:.3e}"
-
-
-def assert_all(results):
-    bad = [msg for ok, msg in results if not ok]
-    assert not bad, "\n".join(bad)
 
 
 def numpy_of(tensors):
@@ -161,10 +150,9 @@ def test_the_workspaces_contents_do_not_matter(kind):
     channel, dropped odd row and short last slice is guarded, so the bits are the same; and a row pitch ld > L with NaN behind
     column L gives the bits of the contiguous call"""
     from riser_amd import _native as nv
-    from riser_amd.train import generic_param_shapes, param_shapes
+    from riser_amd.train import param_shapes
     lib = nv.lib()
-    channels, kernels, depth = T.NETS[kind]
-    shapes = list((param_shapes(channels) if kind == "shipped" else generic_param_shapes(channels, kernels, depth)).values())
+    shapes = list(param_shapes(*T.NETS[kind]).values())
     sd = T.make_state(kind, 11)
     dev = torch.device("cuda", 0)
     h = T.raw_handle(kind, sd, 0)
@@ -236,7 +224,7 @@ def balanced_case(kind):
     seed = {"shipped": 11, "generic": 12}[kind]
     sd = T.make_state(kind, seed)
     x, y = R.make_batch(16, 100, seed + 100)
-    lg = G.torch_loss_and_grads(sd, x, y)[3]
+    lg = R.torch_loss_and_grads(sd, x, y)[3]
     sd["classifier.2.bias"] = sd["classifier.2.bias"].copy()
     sd["classifier.2.bias"][0] += np.float32(np.median(lg[:, 1] - lg[:, 0]))
     return sd, x, y
@@ -246,8 +234,8 @@ def balanced_case(kind):
 @kinds
 def test_evaluate_against_float64(kind):
     sd, x, y = balanced_case(kind)
-    _, _, loss_bar, logits_bar, (l64, _, _, lg64) = G.bars_of(sd, x, y)
-    lg32 = G.torch_loss_and_grads(sd, x, y, torch.float32)[3]
+    _, _, loss_bar, logits_bar, (l64, _, _, lg64) = R.bars_of(sd, x, y)
+    lg32 = R.torch_loss_and_grads(sd, x, y, torch.float32)[3]
     margin = lg64[:, 1] - lg64[:, 0]
     fp32_gap = float(np.abs(lg32 - lg64).max())
     print(f"{kind} evaluate: smallest |l1 - l0| {np.abs(margin).min():.3e}, torch fp32 against float64 logits {fp32_gap:.3e}")
@@ -285,7 +273,7 @@ def test_tied_logits(kind):
     x, y = R.make_batch(3, 100, 111)
     B, n0, n1 = len(y), int((y == 0).sum()), int((y == 1).sum())
     assert n0 != n1
-    bars = G.bars_of(sd, x, y)[0]
+    bars = R.bars_of(sd, x, y)[0]
     t = T.trainer_of(kind, sd)
     try:
         loss, count, logits, grads = T.full_call(t, True, torch.from_numpy(x), torch.from_numpy(y))
@@ -307,7 +295,7 @@ def test_saturated_logits(kind):
     sd = T.make_state(kind, 11)
     sd["classifier.2.weight"] = sd["classifier.2.weight"] * np.float32(1e4)
     x, y = R.make_batch(3, 100, 111)
-    bars, _, loss_bar, logits_bar, (l64, g64, _, lg64) = G.bars_of(sd, x, y)
+    bars, _, loss_bar, logits_bar, (l64, g64, _, lg64) = R.bars_of(sd, x, y)
     assert np.abs(lg64).max() > 1000 and l64 > 100           # a read is wrong by thousands: exp() of it overflows a double
     with np.errstate(over="ignore", divide="ignore"):
         assert np.isinf(np.log(np.exp(lg64).sum(1))).any()

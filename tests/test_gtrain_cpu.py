@@ -1,12 +1,14 @@
 """Training at any depth and any odd kernel (riser_amd.train.GenericTrainer, rs_train_create_generic) without a GPU: the
-float64 references the device tests lean on, the configs taken and refused, the handle's argument checks and the plans."""
+float64 reference the device tests lean on (train_ref) and what it gave for the shipped class before it was the only one, the
+configs taken and refused, the handle's argument checks and the plans."""
 import ctypes as C
+import os
 import types
 
 import numpy as np
 import pytest
 
-import gtrain_ref as G
+import train_ref as R
 from riser_amd import synth
 
 MiB = 1 << 20
@@ -42,7 +44,7 @@ def test_configs_taken_and_refused(lib):
                 fn(cfg)
     with pytest.raises(ValueError, match="dtype"):
         T.GenericTrainer(config_of(ch, [3, 5], 2), dtype="bf16")
-    sd = G.make_state(ch, [3, 5], 2, 1)
+    sd = R.make_state(ch, [3, 5], 2, 1)
     with pytest.raises(ValueError, match="layers.1.2.weight"):
         T.GenericTrainer(config_of(ch, [3, 5], 2), {k: v for k, v in sd.items() if k != "layers.1.2.weight"})
     with pytest.raises(ValueError, match="layers.1.0.weight"):         # kernel 5 where the config says 7
@@ -57,7 +59,7 @@ def test_configs_taken_and_refused(lib):
         with pytest.raises(nv.NativeError, match="no HIP device"):
             T.trainer_for(config_of(ch, [3, 5], 2), sd)
         with pytest.raises(nv.NativeError, match="no HIP device"):
-            T.trainer_for(config_of(ch, [3, 3], 1), G.make_state(ch, [3, 3], 1, 1))
+            T.trainer_for(config_of(ch, [3, 3], 1), R.make_state(ch, [3, 3], 1, 1))
     assert T.is_shipped_class(config_of(ch, [3, 3], 1)) and not T.is_shipped_class(config_of(ch, [3, 3], 2))
     assert not T.is_shipped_class(config_of(ch, [3, 5], 1))
 
@@ -67,20 +69,20 @@ def test_state_dict_layout_is_the_inference_familys(lib):
     from riser_amd.gconv import build_gconv_program
     channels, kernels, depth = [3, 7, 18], [5, 3, 7], 2
     cfg = config_of(channels, kernels, depth)
-    keys, shapes = T.generic_param_keys(3, depth), T.generic_param_shapes(channels, kernels, depth)
+    keys, shapes = T.param_keys(3, depth), T.param_shapes(channels, kernels, depth)
     assert keys[:4] == ["layers.0.0.weight", "layers.0.0.bias", "layers.0.2.weight", "layers.0.2.bias"]
     assert keys[-2:] == ["classifier.2.weight", "classifier.2.bias"] and len(keys) == 2 * 6 + 2 and list(shapes) == keys
     assert shapes["layers.0.0.weight"] == (3, 1, 5) and shapes["layers.0.2.weight"] == (3, 3, 5)
     assert shapes["layers.2.2.weight"] == (18, 18, 7) and shapes["classifier.2.weight"] == (2, 18)
-    sd = T.generic_init_state(channels, kernels, depth)
+    sd = T.init_state(channels, kernels, depth)
     assert {k: tuple(v.shape) for k, v in sd.items()} == shapes
     prog = build_gconv_program(sd, cfg.cnn)
     assert [tuple(cv["w"].shape) for cv in prog["convs"]] == [shapes[k] for k in keys[:-2:2]]
     assert (prog["n_layers"], prog["depth"]) == (3, depth)
-    assert {k: v.shape for k, v in G.make_state(channels, kernels, depth, 1).items()} == shapes
-    # at depth 1 the generic names are the shipped class's
-    assert T.generic_param_keys(4, 1) == T.param_keys(4)
-    assert T.generic_param_shapes([3, 7], [3, 3], 1) == T.param_shapes([3, 7])
+    assert {k: v.shape for k, v in R.make_state(channels, kernels, depth, 1).items()} == shapes
+    # the defaults are the shipped class: depth 1, every kernel 3
+    assert T.param_keys(4, 1) == T.param_keys(4) == [f"layers.{i}.0.{w}" for i in range(4) for w in ("weight", "bias")] + keys[-2:]
+    assert T.param_shapes([3, 7], [3, 3], 1) == T.param_shapes([3, 7])
 
 
 def create_generic(lib, convs, n_layers, depth, device=10 ** 6):
@@ -131,18 +133,18 @@ def test_handle_checks_without_gpu(lib):
 
 
 def plan_handle(channels, kernels, depth):
-    from riser_amd.train import create_generic_handle
-    return create_generic_handle(channels, kernels, depth, G.make_state(channels, kernels, depth, 1), -1)
+    from riser_amd.train import create_handle
+    return create_handle(channels, R.make_state(channels, kernels, depth, 1), -1, kernels, depth, generic=True)
 
 
 def test_slice_plan_and_workspace(lib):
     n, s = C.c_int32(), C.c_int32()
-    channels, kernels, depth, B, L, _ = G.CASES["slices"]
+    channels, kernels, depth, B, L, _ = R.CASES["slices"]
     h = plan_handle(channels, kernels, depth)
     try:
-        for j, (level, ci, co, k) in enumerate(G.convs_of(channels, kernels, depth)):
+        for j, (level, ci, co, k) in enumerate(R.convs_of(channels, kernels, depth)):
             assert lib.rs_train_slice_plan(h, j, B, L, C.byref(n), C.byref(s)) == 0
-            assert (n.value, s.value) == G.slice_plan(B, L, level, ci, co, k), j
+            assert (n.value, s.value) == R.slice_plan(B, L, level, ci, co, k), j
         assert lib.rs_train_slice_plan(h, 0, B, L, C.byref(n), C.byref(s)) == 0
         assert n.value >= 3 and s.value % 4 == 0 and (n.value - 1) * s.value < B * L < n.value * s.value
         assert lib.rs_train_slice_plan(h, 1, B, L, C.byref(n), C.byref(s)) == 0 and n.value * s.value > B * L   # level 0 too
@@ -156,9 +158,9 @@ def test_slice_plan_and_workspace(lib):
         h = plan_handle(channels, kernels, depth)
         try:
             bound_bites = False
-            for j, (level, ci, co, k) in enumerate(G.convs_of(channels, kernels, depth)):
+            for j, (level, ci, co, k) in enumerate(R.convs_of(channels, kernels, depth)):
                 assert lib.rs_train_slice_plan(h, j, B, L, C.byref(n), C.byref(s)) == 0
-                assert (n.value, s.value) == G.slice_plan(B, L, level, ci, co, k), (depth, j)
+                assert (n.value, s.value) == R.slice_plan(B, L, level, ci, co, k), (depth, j)
                 tile = (co * ci * k + co) * 4
                 assert n.value == 1 or n.value * tile <= 32 * MiB, (depth, j)
                 assert (n.value - 1) * s.value < B * (L >> level) <= n.value * s.value
@@ -182,53 +184,57 @@ def test_slice_plan_and_workspace(lib):
 
 
 def test_numpy_backward_equals_float64_autograd():
-    cases = [(name,) + G.case_of(name) for name in G.CASES if name != "slices"] + list(G.special_cases())
-    channels, kernels, depth, _, _, seed = G.CASES["slices"]
-    cases.append(("slices", G.make_state(channels, kernels, depth, seed)) + G.make_batch(2, 1201, seed + 100))
+    cases = [(name,) + R.case_of(name) for name in R.CASES if name != "slices"] + list(R.special_cases())
+    channels, kernels, depth, _, _, seed = R.CASES["slices"]
+    cases.append(("slices", R.make_state(channels, kernels, depth, seed)) + R.make_batch(2, 1201, seed + 100))
     for name, sd, x, y in cases:
-        fwd = G.forward64(sd, x)
-        grads, dys = G.backward64(sd, fwd, y)
-        l64, g64, d64, lg64 = G.torch_loss_and_grads(sd, x, y)
-        assert abs(G.loss64(fwd["logits"], y) - l64) <= 1e-12 * abs(l64), name
-        assert G.gap_of(fwd["logits"], lg64) <= 1e-12, name
-        assert len(dys) == len(d64) == len(G.conv_keys(sd))
+        fwd = R.forward64(sd, x)
+        grads, dys = R.backward64(sd, fwd, y)
+        l64, g64, d64, lg64 = R.torch_loss_and_grads(sd, x, y)
+        assert abs(R.loss64(fwd["logits"], y) - l64) <= 1e-12 * abs(l64), name
+        assert R.gap_of(fwd["logits"], lg64) <= 1e-12, name
+        assert len(dys) == len(d64) == len(R.conv_keys(sd))
         for k in g64:
-            assert G.gap_of(grads[k], g64[k]) <= 1e-12, (name, k)
+            assert R.gap_of(grads[k], g64[k]) <= 1e-12, (name, k)
         for j, (a, b) in enumerate(zip(dys, d64)):
-            assert a.shape == b.shape and G.gap_of(a, b) <= 1e-12, (name, j)
+            assert a.shape == b.shape and R.gap_of(a, b) <= 1e-12, (name, j)
 
 
-def test_depth_one_kernel_three_is_train_ref():
-    """at the shipped class the generic reference is the one the shipped tests use"""
-    import train_ref as R
-    sd = R.make_state([3, 7, 18], 5)
+def test_depth_one_kernel_three_is_the_recorded_shipped_reference():
+    """at the shipped class the reference gives, bit for bit, what the depth-1, kernel-3 reference it replaced gave: that
+    module's gradients, per-layer dY and fragile masks are tests/golden/train_ref_shipped.npz"""
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_ref_shipped.npz"))
+    sd = R.make_state([3, 7, 18], [3] * 3, 1, 5)
     x, y = R.make_batch(3, 100, 6)
-    a, b = R.forward64(sd, x), G.forward64(sd, x)
-    ga, da = R.backward64(sd, a, y)
-    gb, db = G.backward64(sd, b, y)
-    assert all(np.array_equal(ga[k], gb[k]) for k in ga) and all(np.array_equal(p, q) for p, q in zip(da, db))
-    assert all(np.array_equal(p, q) for p, q in zip(R.fragile(a), G.fragile(b)))
+    fwd = R.forward64(sd, x)
+    grads, dys = R.backward64(sd, fwd, y)
+    got = {f"grad.{k}": v for k, v in grads.items()}
+    got.update({f"dy.{l}": v for l, v in enumerate(dys)})
+    got.update({f"fragile.{l}": v for l, v in enumerate(R.fragile(fwd))})
+    assert sorted(got) == sorted(want.files) and len(got) == 8 + 3 + 3
+    for k in got:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
 
 
 def test_fragile_share_of_the_committed_seeds():
-    for name in G.CASES:
-        sd, x, y = G.case_of(name)
-        share = G.fragile_share(G.forward64(sd, x))
+    for name in R.CASES:
+        sd, x, y = R.case_of(name)
+        share = R.fragile_share(R.forward64(sd, x))
         print(f"{name}: fragile share {share:.3e}")
-        assert share == 0 if name in G.SMALL else share < 1e-4, (name, share)
-    for name, sd, x, y in G.special_cases():
-        assert G.fragile_share(G.forward64(sd, x)) == 0, name
+        assert share == 0 if name in R.SMALL else share < 1e-4, (name, share)
+    for name, sd, x, y in R.special_cases():
+        assert R.fragile_share(R.forward64(sd, x)) == 0, name
 
 
 def test_planted_defects_miss_by_more_than_ten_bars():
     """each defect planted in the float64 reference must be far outside the bars the device is held to"""
-    sd, x, y = G.case_of("depth2")
-    bars, dbars, _, _, _ = G.bars_of(sd, x, y)
-    fwd = G.forward64(sd, x)
-    good, good_dy = G.backward64(sd, fwd, y)
-    for defect in G.DEFECTS:
-        grads, dys = G.backward64(sd, fwd, y, defect=defect)
-        worst = max([G.gap_of(grads[k], good[k]) / bars[k] for k in good] +
-                    [G.gap_of(a, b) / d for a, b, d in zip(dys, good_dy, dbars)])
+    sd, x, y = R.case_of("depth2")
+    bars, dbars, _, _, _ = R.bars_of(sd, x, y)
+    fwd = R.forward64(sd, x)
+    good, good_dy = R.backward64(sd, fwd, y)
+    for defect in sorted(set(R.GENERIC_DEFECTS + R.SHIPPED_DEFECTS[1:])):         # the pooling defects at depth 2 as well
+        grads, dys = R.backward64(sd, fwd, y, defect=defect)
+        worst = max([R.gap_of(grads[k], good[k]) / bars[k] for k in good] +
+                    [R.gap_of(a, b) / d for a, b, d in zip(dys, good_dy, dbars)])
         print(f"{defect}: {worst:.3g} bars")
         assert worst > 10, defect

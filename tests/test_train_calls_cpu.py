@@ -5,7 +5,6 @@ import numpy as np
 import pytest
 import torch
 
-import gtrain_ref as G
 import train_calls_ref as T
 import train_ref as R
 
@@ -31,7 +30,7 @@ def test_planted_adam_defects_miss_by_more_than_ten_bars(kind):
     x, y = R.make_batch(3, 100, 111)
     grads, cur = [], dict(sd)
     for t in range(1, T.ADAM_STEPS + 1):
-        grads.append(G.torch_loss_and_grads(cur, x, y)[1])
+        grads.append(R.torch_loss_and_grads(cur, x, y)[1])
         cur = {k: v.astype(np.float32) for k, v in T.numpy_adam_on(sd, grads, checked=(t,))[t].items()}
     p64, p32 = T.torch_adam_on(sd, grads, torch.float64), T.torch_adam_on(sd, grads, torch.float32)
     bars = T.adam_bars(p32, p64)
@@ -73,7 +72,7 @@ def test_max_batch_promises_only_what_the_launches_take(lib, kind):
             for name, (gx, gy, gz) in T.launch_grids(kind, mb, L, lambda j: plans[j][0]):
                 assert 1 <= gx <= T.GRID_X and 1 <= gy <= T.GRID_YZ and 1 <= gz <= T.GRID_YZ, (L, mb, name, (gx, gy, gz))
         if kind == "shipped":                                # the shipped class's own numbers are what they were
-            assert T.slice_plan_of(lib, h, 0, 3, 100) == G.slice_plan(3, 100, 0, 1, 3, 3)
+            assert T.slice_plan_of(lib, h, 0, 3, 100) == R.slice_plan(3, 100, 0, 1, 3, 3)
     finally:
         lib.rs_train_destroy(h)
 

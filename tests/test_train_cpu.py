@@ -1,5 +1,5 @@
-"""Training (riser_amd.train, csrc/train.hip, rs_train_*) without a GPU: the float64 references the device tests lean on, the
-C ABI's argument checks, the refusals, and the loop of riser/train.py on a stub trainer."""
+"""Training (riser_amd.train, csrc/train.hip, rs_train_*) without a GPU: the float64 reference the device tests lean on (train_ref, here at the
+shipped class: depth 1, every kernel 3), the C ABI's argument checks, the refusals, and the loop of riser/train.py on a stub trainer."""
 import ctypes as C
 import os
 import re
@@ -24,13 +24,17 @@ def config_of(channels, **over):
     return types.SimpleNamespace(**{"model": "cnn", "learning_rate": 1e-3, "cnn": cnn, **over})
 
 
+def state_of(channels, seed, bias=None):
+    return R.make_state(channels, [3] * len(channels), 1, seed, bias)
+
+
 def small_cases():
     channels, B, L, seed = SMALL
-    sd = R.make_state(channels, seed)
+    sd = state_of(channels, seed)
     x, y = R.make_batch(B, L, seed + 100)
     yield "random", sd, x, y
-    yield "ties", sd, np.repeat(np.array([0.75, -1.25, 0.5], np.float32)[:, None], 200, axis=1), np.array([1, 0, 1])
-    yield "dead", R.make_state(channels, seed, bias=-50.0), x, y
+    yield "ties", sd, *R.constant_reads(3, 200)
+    yield "dead", state_of(channels, seed, bias=-50.0), x, y
 
 
 def test_numpy_backward_equals_float64_autograd():
@@ -63,7 +67,7 @@ def test_small_shapes_have_no_fragile_element():
 
 def test_fragile_share_of_the_large_shapes():
     for channels, B, L, seed in LARGE:
-        frag = R.fragile(R.forward64(R.make_state(channels, seed), R.make_batch(B, L, seed + 100)[0]))
+        frag = R.fragile(R.forward64(state_of(channels, seed), R.make_batch(B, L, seed + 100)[0]))
         share = sum(int(f.sum()) for f in frag) / sum(f.size for f in frag)
         print(f"{len(channels)} layers, {B} x {L}: fragile share {share:.3e}")
         assert share < 1e-4, (channels[:3], share)
@@ -79,7 +83,7 @@ def lib():
 
 def plan_handle(channels):
     from riser_amd.train import create_handle
-    return create_handle(channels, R.make_state(channels, 1), -1)
+    return create_handle(channels, state_of(channels, 1), -1)
 
 
 def test_header_symbols_and_sources_agree(lib):
@@ -194,7 +198,7 @@ def test_refusals_come_before_any_gpu_call():
     with pytest.raises(ValueError, match="dtype"):
         Trainer(config_of(ch), dtype="bf16")
     with pytest.raises(ValueError, match="layers.1.0.weight"):
-        Trainer(config_of(ch), {k: v for k, v in R.make_state(ch, 1).items() if k != "layers.1.0.weight"})
+        Trainer(config_of(ch), {k: v for k, v in state_of(ch, 1).items() if k != "layers.1.0.weight"})
     assert check_config(config_of(ch)) == ch
 
 

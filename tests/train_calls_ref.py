@@ -1,20 +1,18 @@
 """Helpers of the call-surface tests of the training family (test_gpu_train_calls.py, test_train_calls_cpu.py): the two small
-nets the suite already trains - the shipped class as `Trainer`, gtrain_ref.CASES["depth2"] as `GenericTrainer` - and Adam on
-given gradients.  No reference of the net lives here: float64 comes from gtrain_ref, whose torch net and `bars_of` take the
-shipped class's state dicts as they are (depth 1, kernels of 3).
+nets the suite already trains - the shipped class, which riser_amd.train.trainer_for gives a `Trainer`, and
+train_ref.CASES["depth2"], which it gives a `GenericTrainer` - and Adam on given gradients.  No reference of the net lives
+here: float64 comes from train_ref, the trainers from train_device.
 """
 import ctypes as C
-import types
 
 import numpy as np
 import torch
 
-import gtrain_ref as G
+import train_device as D
 import train_ref as R
-from riser_amd import synth
 
 KINDS = ("shipped", "generic")
-NETS = {"shipped": ([3, 7, 18, 37], [3, 3, 3, 3], 1), "generic": G.CASES["depth2"][:3]}
+NETS = {"shipped": ([3, 7, 18, 37], [3, 3, 3, 3], 1), "generic": R.CASES["depth2"][:3]}     # (channels, kernels, depth)
 ADAM_STEPS, ADAM_LR_CHANGE, ADAM_LRS = 40, 20, (1e-3, 3e-3)        # steps 1-20 at the first rate, 21-40 at the second
 ADAM_CHECKED = (1, 2, 20, 21, 40)
 ADAM_DEFECTS = ("no_first_correction", "no_second_correction", "eps_inside_sqrt", "betas_swapped", "step_stuck_at_1",
@@ -27,35 +25,23 @@ def min_length(kind):
 
 
 def make_state(kind, seed, bias=None):
-    channels, kernels, depth = NETS[kind]
-    return R.make_state(channels, seed, bias) if kind == "shipped" else G.make_state(channels, kernels, depth, seed, bias)
-
-
-def config_of(kind, lr=1e-3):
-    channels, kernels, depth = NETS[kind]
-    return types.SimpleNamespace(model="cnn", learning_rate=lr, cnn=synth.CnnConfig(channels=channels, kernels=kernels, depth=depth))
+    return R.make_state(*NETS[kind], seed, bias)
 
 
 def trainer_of(kind, sd, lr=1e-3):
-    from riser_amd.train import GenericTrainer, Trainer
-    cls = Trainer if kind == "shipped" else GenericTrainer
-    return cls(config_of(kind, lr), sd, device=torch.device("cuda", 0))
+    return D.trainer_of(NETS[kind], sd, lr)
 
 
 def raw_handle(kind, sd, device_index):
-    """the C handle of either constructor; device_index < 0: without device memory"""
-    from riser_amd.train import create_generic_handle, create_handle
+    """the C handle of the net's own constructor; device_index < 0: without device memory"""
+    from riser_amd.train import create_handle
     channels, kernels, depth = NETS[kind]
-    sd = {k: np.ascontiguousarray(v, np.float32) for k, v in sd.items()}
-    if kind == "shipped":
-        return create_handle(channels, sd, device_index)
-    return create_generic_handle(channels, kernels, depth, sd, device_index)
+    return create_handle(channels, {k: np.ascontiguousarray(v, np.float32) for k, v in sd.items()}, device_index, kernels, depth)
 
 
 def conv_shapes(kind):
     """[(level, c_in, c_out, k)] per conv, j = layer * depth + d"""
-    channels, kernels, depth = NETS[kind]
-    return list(G.convs_of(channels, kernels, depth))
+    return list(R.convs_of(*NETS[kind]))
 
 
 def batch_of(B, L, seed):

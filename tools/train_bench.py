@@ -43,7 +43,7 @@ def state_of(cfg):
     if T.is_shipped_class(cfg):
         return {k: torch.from_numpy(v) for k, v in synth.make_state_dict(1).items()}
     torch.manual_seed(1)
-    return T.generic_init_state(*T.check_generic_config(cfg))
+    return T.init_state(*T.check_generic_config(cfg))
 
 
 def torch_net(state, dev, cfg):
