@@ -685,6 +685,58 @@ RS_API int rs_train_set_params(rs_train* h, int index, const float* src, size_t 
 RS_API int rs_train_get_grads(rs_train* h, int index, float* dst, size_t count);
 RS_API int rs_train_debug_copy(rs_train* h, int layer, int what, void* d_dst, size_t bytes);
 
+/* Added after ABI 2.9, rs_version unchanged: TCN training (riser/nets/tcn.py as riser/train.py builds it) through the receptive
+ * cone of the last sample alone - csrc/tcn_train.hip.  fp32, two classes, one input channel, B reads of ONE length L >= 1 per
+ * call (pitch ld >= L; lengths below the receptive field are legal).  The calls mean what their rs_train_* namesakes mean and
+ * return their statuses; only the differences are stated here.
+ * rs_tcn_train_create: RS_ERR_ARG before a device is touched for `bottleneck` != 0 (tcn-bot), a dtype other than RS_F32,
+ * n_classes != 2, in_channels != 1, kernel < 2, dropout outside [0, 1).  `tensors` are host arrays in the order of the flat
+ * parameter vector and of the tensor index of get_params / set_params / get_grads: per block weight_g [F], weight_v
+ * [F][c_in][k], bias [F] of conv1, the same of conv2, then - only where c_in != n_filters, i.e. where the reference applies
+ * it - the shortcut's weight [F][c_in] and bias; after the blocks the Linear [2][F] and its bias.  A shortcut the reference
+ * builds but never applies has no tensor here: it takes no gradient and no update.  device < 0: a handle without device memory.
+ * rs_tcn_train_slice_plan: conv `which` (0 conv1, 1 conv2, 2 an applied shortcut) of `block` contracts B * rows positions (the
+ * rows per read of its output gradient inside the cone) in n_slices of slice_len.
+ * rs_tcn_train_max_batch promises what every launch and the 2 GiB window take.
+ * Dropout: element (conv c, read b, q, channel ch) - c = 2 block for conv1, 2 block + 1 for conv2; q = L-1 - position, the
+ * distance from the read's last sample, so that a longer read gives the bits of its own tail - is kept iff
+ *     mix(mix(mix(key_c + b) + q) + ch) >= floor(p * 2^32),
+ *     key_c = mix(mix(mix(mix(mix(lo32(seed) + 0x9e3779b9) + hi32(seed)) + lo32(counter)) + hi32(counter)) + c),
+ *     mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16        (all in 32-bit unsigned)
+ * and a kept element is scaled by the fp32 value of 1 / (1 - p).  `counter` counts the rs_tcn_train_forward_backward calls on
+ * the handle that returned RS_OK; rs_tcn_train_set_dropout sets p, the seed and the counter.  rs_tcn_train_evaluate is eval
+ * mode: no mask.  p = 0 applies none.
+ * rs_tcn_train_debug_copy (test hook): block `block`'s a1 = drop(relu(conv1)) (what 0) on the rows conv2 reads, a2 =
+ * drop(relu(conv2)) (1) and out = relu(a2 + residual) (2) on the rows the next block reads, and the raw gradients arriving at
+ * a1 (3) and at out (4), position-major [B][rows][n_filters padded to 4], row m at position L-1 - dilation_block * m (a2, out:
+ * * base).  RS_ERR_ARG after an rs_tcn_train_evaluate or a refused call, as rs_train_debug_copy. */
+typedef struct rs_tcn_train rs_tcn_train;
+typedef struct {
+    int32_t n_layers, n_filters, kernel, dilation;
+    int32_t in_channels, n_classes;
+    int32_t dtype;              /* rs_dtype: RS_F32 */
+    int32_t bottleneck;         /* 0: riser/nets/tcn.py */
+    double dropout;
+    uint64_t seed;
+} rs_tcn_train_config;
+RS_API int rs_tcn_train_create(const rs_tcn_train_config* cfg, const float* const* tensors, int n_tensors, int device,
+                               rs_tcn_train** out);
+RS_API int rs_tcn_train_destroy(rs_tcn_train* h);
+RS_API size_t rs_tcn_train_workspace_bytes(const rs_tcn_train* h, int B, int L);
+RS_API int rs_tcn_train_max_batch(const rs_tcn_train* h, int L);
+RS_API int rs_tcn_train_slice_plan(const rs_tcn_train* h, int block, int which, int B, int L, int32_t* n_slices,
+                                   int32_t* slice_len, int32_t* rows);
+RS_API int rs_tcn_train_forward_backward(rs_tcn_train* h, const float* d_x, const int32_t* d_labels, int B, int L, int ld,
+                                         void* d_ws, size_t ws_bytes, float* d_out, void* stream);
+RS_API int rs_tcn_train_evaluate(rs_tcn_train* h, const float* d_x, const int32_t* d_labels, int B, int L, int ld, void* d_ws,
+                                 size_t ws_bytes, float* d_out, void* stream);
+RS_API int rs_tcn_train_set_dropout(rs_tcn_train* h, double p, uint64_t seed, int64_t counter);
+RS_API int rs_tcn_train_adam_step(rs_tcn_train* h, float lr, float beta1, float beta2, float eps, void* stream);
+RS_API int rs_tcn_train_get_params(rs_tcn_train* h, int index, float* dst, size_t count);
+RS_API int rs_tcn_train_set_params(rs_tcn_train* h, int index, const float* src, size_t count);
+RS_API int rs_tcn_train_get_grads(rs_tcn_train* h, int index, float* dst, size_t count);
+RS_API int rs_tcn_train_debug_copy(rs_tcn_train* h, int block, int what, void* d_dst, size_t bytes);
+
 /* Half precision has a range: RS_F16 / RS_F16X3 / RS_F16XF8 store activations as IEEE half, and a value beyond 65504 leaves the
  * conversion as +inf - the forward pass goes on, the probabilities of that read are wrong, and the reference's fp32 path
  * (riser/model.py:22-28) has no such failure.  Every kernel epilogue of those modes checks its conversions and raises a sticky flag

@@ -36,6 +36,10 @@ SYMBOLS = (
     "rs_train_create", "rs_train_destroy", "rs_train_workspace_bytes", "rs_train_max_batch", "rs_train_slice_plan",
     "rs_train_forward_backward", "rs_train_evaluate", "rs_train_adam_step", "rs_train_get_params", "rs_train_set_params",
     "rs_train_get_grads", "rs_train_debug_copy", "rs_train_create_generic",
+    "rs_tcn_train_create", "rs_tcn_train_destroy", "rs_tcn_train_workspace_bytes", "rs_tcn_train_max_batch",
+    "rs_tcn_train_slice_plan", "rs_tcn_train_forward_backward", "rs_tcn_train_evaluate", "rs_tcn_train_set_dropout",
+    "rs_tcn_train_adam_step", "rs_tcn_train_get_params", "rs_tcn_train_set_params", "rs_tcn_train_get_grads",
+    "rs_tcn_train_debug_copy",
 )
 
 
@@ -227,6 +231,28 @@ def lib():
         fn.argtypes = [vp, i32, vp, sz]
     L.rs_train_debug_copy.restype = i32
     L.rs_train_debug_copy.argtypes = [vp, i32, i32, vp, sz]
+    L.rs_tcn_train_create.restype = i32
+    L.rs_tcn_train_create.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
+    L.rs_tcn_train_destroy.restype = i32
+    L.rs_tcn_train_destroy.argtypes = [vp]
+    L.rs_tcn_train_workspace_bytes.restype = sz
+    L.rs_tcn_train_workspace_bytes.argtypes = [vp, i32, i32]
+    L.rs_tcn_train_max_batch.restype = i32
+    L.rs_tcn_train_max_batch.argtypes = [vp, i32]
+    L.rs_tcn_train_slice_plan.restype = i32
+    L.rs_tcn_train_slice_plan.argtypes = [vp, i32, i32, i32, i32] + [C.POINTER(C.c_int32)] * 3
+    for fn in (L.rs_tcn_train_forward_backward, L.rs_tcn_train_evaluate):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, vp, vp]
+    L.rs_tcn_train_set_dropout.restype = i32
+    L.rs_tcn_train_set_dropout.argtypes = [vp, C.c_double, C.c_uint64, i64]
+    L.rs_tcn_train_adam_step.restype = i32
+    L.rs_tcn_train_adam_step.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, vp]
+    for fn in (L.rs_tcn_train_get_params, L.rs_tcn_train_set_params, L.rs_tcn_train_get_grads):
+        fn.restype = i32
+        fn.argtypes = [vp, i32, vp, sz]
+    L.rs_tcn_train_debug_copy.restype = i32
+    L.rs_tcn_train_debug_copy.argtypes = [vp, i32, i32, vp, sz]
     L.rs_polya_end_resume.restype = i32
     L.rs_polya_end_resume.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.rs_debug_capture_layer.restype = i32

@@ -31,6 +31,7 @@
 //                            the first one the bias column; the second kernel adds the partials in ascending slice order.
 //                            No floating-point atomics anywhere.  Both dZ forms feed it.
 //   train_adam_kernel        one launch over the flat master parameters, torch.optim.Adam's defaults and operation order.
+//                            It, train_loss_kernel and train_reduce_kernel live in train/kernels.hpp, shared with tcn_train.hip.
 //   train_pack_kernel        per conv, after every update: the two zero-padded forms the MFMA loops read,
 //                            [k][p16(c_in)][p16(c_out)] (forward) and [k][p16(c_out)][p16(c_in)] (data gradient).
 //
@@ -39,6 +40,7 @@
 #include "device_prelude.hpp"
 #include "family/host.hpp"
 #include "gconv/plan.hpp"
+#include "train/kernels.hpp"
 #include "train/plan.hpp"
 
 #include <cmath>
@@ -332,17 +334,6 @@ __global__ __launch_bounds__(64) void train_wgrad_kernel(const WgradArgs a) {
         }
 }
 
-// grad[i] = partial[0][i] + partial[1][i] + ..., ascending
-__global__ __launch_bounds__(256) void train_reduce_kernel(const float* __restrict__ partial, int n_slices, int64_t n,
-                                                           float* __restrict__ grad) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float s = partial[i];
-#pragma unroll 8
-    for (int k = 1; k < n_slices; ++k) s += partial[(int64_t)k * n + i];
-    grad[i] = s;
-}
-
 // GAP over the T rows of read b (ascending) and the two logits (a fixed tree over the block)
 __global__ __launch_bounds__(256) void train_head_kernel(const float* __restrict__ y, int T, int pitch, int C,
                                                          const float* __restrict__ fcw, const float* __restrict__ fcb,
@@ -369,32 +360,6 @@ __global__ __launch_bounds__(256) void train_head_kernel(const float* __restrict
         __syncthreads();
     }
     if (threadIdx.x < 2) logits[2 * b + threadIdx.x] = red[threadIdx.x][0] + fcb[threadIdx.x];
-}
-
-// out[0] = mean loss, out[1] = reads whose argmax is their label, out[2 ..] = logits (already there); dlogits; flag[0] = 1
-// where a label is outside {0, 1}.  One thread: B terms in read order.
-__global__ void train_loss_kernel(float* __restrict__ out, const int32_t* __restrict__ labels, int B,
-                                  float* __restrict__ dlogits, int32_t* __restrict__ flag) {
-    if (threadIdx.x || blockIdx.x) return;
-    double loss = 0.0;
-    int correct = 0, bad = 0;
-    for (int b = 0; b < B; ++b) {
-        const double l0 = out[2 + 2 * b], l1 = out[3 + 2 * b];
-        int y = labels[b];
-        if (y < 0 || y > 1) {
-            bad = 1;
-            y = 0;
-        }
-        const double mx = fmax(l0, l1);
-        const double lse = mx + log(exp(l0 - mx) + exp(l1 - mx));
-        loss += lse - (y ? l1 : l0);
-        correct += ((l1 > l0) ? 1 : 0) == y;                // argmax takes the first of equal logits
-        dlogits[2 * b] = (float)((exp(l0 - lse) - (y == 0 ? 1.0 : 0.0)) / B);
-        dlogits[2 * b + 1] = (float)((exp(l1 - lse) - (y == 1 ? 1.0 : 0.0)) / B);
-    }
-    out[0] = (float)(loss / B);
-    out[1] = (float)correct;
-    flag[0] = bad;
 }
 
 // dW_fc[j][c] = sum_b dlogits[b][j] gap[b][c], db_fc[j] = sum_b dlogits[b][j], ascending b
@@ -427,20 +392,6 @@ __global__ __launch_bounds__(256) void train_head_bwd_kernel(const float* __rest
         const float v = fmaf(d1, fcw[C + c], d0 * fcw[c]) / (float)T;
         for (int t = blockIdx.x; t < T; t += gridDim.x) dy[((int64_t)b * T + t) * pitch + c] = v;
     }
-}
-
-// torch.optim.Adam (no weight decay, no amsgrad): step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), both from the host
-__global__ __launch_bounds__(256) void train_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, int64_t n, float beta1,
-                                                         float beta2, float step_size, float bc2_sqrt, float eps) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float gi = g[i];
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
 }
 
 // master W [c_out][c_in][kt] -> wf [kt][p16(c_in)][p16(c_out)] and wt [kt][p16(c_out)][p16(c_in)], zero padded; kt = 3 (K3) or k
